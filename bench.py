@@ -8,8 +8,13 @@ post-processing) -> Cells/Cytoplasm -> object tables -> shape/intensity/texture
 features for Nuclei, Cells, Cytoplasm -> results copied to the host.  Multi-GPU: one process per
 GPU, FOVs (wells) sharded by rank, no data-path collective (scaling "weak").
 
-  python bench.py [--gpus N --steps K --warmup W --batch B]
+  python bench.py [--gpus N --steps K --warmup W --batch B] [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --dump-outputs DIR
+also writes the last timed step's results as DIR/<name>.npy.  --full adds what takes runs of its
+own: the instrumented per-stage steps and rooflines, the measured HBM copy bandwidth and the CPU
+baseline.
 """
 from __future__ import annotations
 
@@ -40,8 +45,15 @@ def parse():
     ap.add_argument("--size", type=int, default=2080)
     ap.add_argument("--channels", type=int, default=5)
     ap.add_argument("--weights", default=None, help="CPnet state_dict (default: seeded random init)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--stage-steps", type=int, default=3, help="instrumented steps after timing (>= 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the instrumented per-stage steps (stage_ms_per_step, "
+                         "roofline, roofline_all), the HBM copy measurement and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the last timed step (what FovPipeline.fetch returned) as "
+                         "DIR/<name>.npy (float64; at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--stage-steps", type=int, default=3,
+                    help="--full: instrumented steps after timing (>= 1)")
     ap.add_argument("--pipes", type=int, default=2,
                     help="pipelines (own libcpx context, buffers and HIP stream) per GPU: step i "
                          "runs on pipeline i %% pipes, so that many batches are in flight")
@@ -82,7 +94,7 @@ def main():
         local = int(os.environ["CPX_BENCH_DEVICE"])
     # the CPU baseline's worker processes fork from a server started before this process
     # touches the GPU (no fork or exec of a GPU-initialised process)
-    cpu_ctx = _cpu_pool_context() if (rank == 0 and world == 1 and not a.no_cpu_baseline) else None
+    cpu_ctx = _cpu_pool_context() if (a.full and rank == 0 and world == 1 and not a.no_cpu_baseline) else None
     torch.cuda.set_device(local)
     if world > 1:
         # barrier + max/sum reductions of two host scalars only: gloo (no RCCL on the data path)
@@ -158,6 +170,8 @@ def main():
         if world > 1:
             dist.barrier()
 
+    last = [None]  # the results of the step fetched last (--dump-outputs)
+
     def run_steps(batches, record=None):
         """One step per batch index of `batches` (an iterable: a range, or the claims from the
         shared work queue), every step's results fetched to the host.  Up to P + 1 steps are
@@ -169,6 +183,7 @@ def main():
         def fetch_oldest():
             q, slot = pend.pop(0)
             res = q.fetch(slot)
+            last[0] = res
             if record is not None:
                 record.append([int(res.hdr[s]["n_objects"].sum()) for s in ("Nuclei", "Cells", "Cytoplasm")])
         for k in batches:
@@ -213,6 +228,55 @@ def main():
     dt = shard.max_over_ranks(time.perf_counter() - t0)
     total_fovs = shard.sum_over_ranks(n_done * B)
     value = total_fovs / dt
+
+    if a.dump_outputs and last[0] is not None:
+        dump_outputs(a.dump_outputs if world == 1 else os.path.join(a.dump_outputs, f"rank{rank}"), last[0])
+
+    n_tiles = pipe.seg.geom.n_tiles
+    line = {
+        "metric": "fields-of-view/sec, 2080x2080x5ch illum+seg+feat pipe",
+        "value": round(value, 2),
+        "unit": "FOV/s",
+        "n_gpus": world,
+        "steps": a.steps,
+        "warmup": a.warmup,
+        "ms_per_step": round(dt / a.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": ("fp32 planes / fp64 QC+features / " +
+                  {"f16x3": "fp32 CPnet (split-fp16 MFMA, f16x3)", "bf16": "bf16 CPnet",
+                   "fp32": "fp32 CPnet (eager PyTorch)"}[a.cpnet_precision]),
+        "data": (f"synthetic ({'pinned-host uint16 plates copied to the GPU inside every step (PCIe-inclusive)' if a.host_inputs else 'HBM-resident uint16 plates'}, "
+                 f"Poisson background, Gaussian nuclei + halos; "
+                 f"{a.pool} distinct batches = {a.pool * B} distinct FOVs per GPU, cycled)"),
+        "config": {"workload": ("configs[1]: 384-well plate, 1 FOV/well, 2080x2080x5ch, illum->seg->feat"
+                                if Z <= 1 else
+                                f"configs[4] variant: {H}x{W}x{C}ch x {Z} z-planes, z-max->illum->seg->feat"),
+                   "fovs_per_step": B * world, "batch_per_gpu": B, "H": H, "W": W, "C": C,
+                   "cellpose_model": cfg.model, "diameter": cfg.diameter,
+                   "cpnet_weights": os.path.basename(weights) if weights else "seeded-random-init",
+                   "tiles_per_fov": n_tiles, "parallelism": f"fov-sharded x{world}",
+                   "scheduler": ("shared work queue (cpx.plate.WorkQueue)" if queue is not None
+                                 else "static per-rank steps"),
+                   "steps_this_rank": n_done,
+                   "batches_in_flight_per_gpu": len(pipes)},
+        "objects_per_fov": ([round(x / (B * world) * world, 1) for x in np.mean(np.array(n_obj), axis=0)]
+                            if n_obj else None),
+    }
+
+    def finish():
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            barrier()
+            if queue is not None and rank == 0:
+                import shutil
+                shutil.rmtree(os.path.dirname(queue.path), ignore_errors=True)
+            dist.destroy_process_group()
+
+    if not a.full:
+        return finish()
 
     # ---- instrumented steps (outside the timed region): per-stage device time by HIP events on
     # the stream every stage is launched on (torch's current stream; libcpx is bound to it)
@@ -294,7 +358,6 @@ def main():
     per_step_ms = {k: v / a.stage_steps for k, v in acc.items()}
     sub_ms = {k: v / a.stage_steps for k, v in sub.items()}
     N = H * W
-    n_tiles = pipe.seg.geom.n_tiles
     # algorithmic bytes / flops per launch (one batch of B FOVs)
     illum_bytes = B * C * N * (2 + 4 + 4)                # raw u16 + illum f32 in, fp32 plane out
     # the C fp32 planes once per step plus one int32 label image per object set
@@ -400,53 +463,52 @@ def main():
                  "peak_source": "tools/micro/lds_atomic.hip (random 32K-word no-return atomics), profiles/r05p_lds_atomic.log"}
 
     dominant = max(kernels, key=lambda k: kernels[k]["ms"])
-    line = {
-        "metric": "fields-of-view/sec, 2080x2080x5ch illum+seg+feat pipe",
-        "value": round(value, 2),
-        "unit": "FOV/s",
-        "n_gpus": world,
-        "steps": a.steps,
-        "warmup": a.warmup,
-        "ms_per_step": round(dt / a.steps * 1e3, 3),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": ("fp32 planes / fp64 QC+features / " +
-                  {"f16x3": "fp32 CPnet (split-fp16 MFMA, f16x3)", "bf16": "bf16 CPnet",
-                   "fp32": "fp32 CPnet (eager PyTorch)"}[a.cpnet_precision]),
-        "data": (f"synthetic ({'pinned-host uint16 plates copied to the GPU inside every step (PCIe-inclusive)' if a.host_inputs else 'HBM-resident uint16 plates'}, "
-                 f"Poisson background, Gaussian nuclei + halos; "
-                 f"{a.pool} distinct batches = {a.pool * B} distinct FOVs per GPU, cycled)"),
-        "config": {"workload": ("configs[1]: 384-well plate, 1 FOV/well, 2080x2080x5ch, illum->seg->feat"
-                                if Z <= 1 else
-                                f"configs[4] variant: {H}x{W}x{C}ch x {Z} z-planes, z-max->illum->seg->feat"),
-                   "fovs_per_step": B * world, "batch_per_gpu": B, "H": H, "W": W, "C": C,
-                   "cellpose_model": cfg.model, "diameter": cfg.diameter,
-                   "cpnet_weights": os.path.basename(weights) if weights else "seeded-random-init",
-                   "tiles_per_fov": n_tiles, "parallelism": f"fov-sharded x{world}",
-                   "scheduler": ("shared work queue (cpx.plate.WorkQueue)" if queue is not None
-                                 else "static per-rank steps"),
-                   "steps_this_rank": n_done,
-                   "batches_in_flight_per_gpu": len(pipes)},
-        "objects_per_fov": ([round(x / (B * world) * world, 1) for x in np.mean(np.array(n_obj), axis=0)]
-                            if n_obj else None),
+    line.update({
         "stage_ms_per_step": {k: round(v, 3) for k, v in {**per_step_ms, **sub_ms}.items()},
         "roofline": roof(dominant),
         "roofline_all": {**{k: roof(k) for k in kernels}, "glcm": glcm_roof, "follow": follow_roof,
                          "flow_error_reg": fe_roof},
         "hbm_copy_measured_GBs": round(copy_gbs, 1),
-    }
+    })
     if cpu_ctx is not None:
         line["cpu_baseline"] = cpu_baseline(cpu_ctx, pipe.raw if (Z > 1 or a.host_inputs) else pool[0], illum,
                                             C, H, W, cfg)
-    if rank == 0:
-        print(json.dumps(line), flush=True)
-    if world > 1:
-        barrier()
-        if queue is not None and rank == 0:
-            import shutil
-            shutil.rmtree(os.path.dirname(queue.path), ignore_errors=True)
-        dist.destroy_process_group()
+    finish()
+
+
+def dump_outputs(path, res, limit=64_000_000):
+    """Write one step's FovResults (what FovPipeline.fetch returned to the timed loop) as
+    path/<name>.npy, float64: qc [B*C, 2] (slope, pct_max), failed / recovered [B], and per object
+    set n_objects [B], objects [n, 12] (label, area, bbox x 4, centroid_r, centroid_c, yc, xc,
+    kept, cell_idx) and features [n, F], the FOVs' rows concatenated in batch order.  If the
+    arrays exceed `limit` bytes in all, the object and feature tables keep a fixed seeded sample
+    of their rows (the same rows of both, in order)."""
+    import numpy as np
+    from cpx.pipeline import OBJECT_SETS
+    os.makedirs(path, exist_ok=True)
+    out = {"qc": np.stack([res.qc["slope"], res.qc["pct_max"]], axis=1),
+           "failed": np.asarray(res.failed), "recovered": np.asarray(res.recovered)}
+    tables = {}
+    for s in OBJECT_SETS:
+        out[f"n_objects_{s}"] = res.hdr[s]["n_objects"]
+        o = np.concatenate(res.objects[s])
+        tables[f"objects_{s}"] = np.column_stack(
+            [o["label"], o["area"], o["bbox"], o["centroid_r"], o["centroid_c"], o["yc"], o["xc"],
+             o["kept"], o["cell_idx"]]).reshape(len(o), 12)
+        tables[f"features_{s}"] = np.concatenate(res.feats[s])
+    row_bytes = {s: 8 * (12 + tables[f"features_{s}"].shape[1]) for s in OBJECT_SETS}
+    total = sum(row_bytes[s] * len(tables[f"objects_{s}"]) for s in OBJECT_SETS)
+    room = limit - (1 << 20)  # the small arrays and the .npy headers
+    rng = np.random.default_rng(0)
+    for s in OBJECT_SETS:
+        n = len(tables[f"objects_{s}"])
+        if total > room:
+            keep = np.sort(rng.choice(n, int(n * room / total), replace=False))
+            for k in (f"objects_{s}", f"features_{s}"):
+                tables[k] = tables[k][keep]
+    out.update(tables)
+    for name, arr in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
 
 
 def pmc_traffic(batch, precision):

@@ -133,11 +133,12 @@ def test_launch_two_processes_one_gpu_byte_identical(tmp_path, dev):
         assert filecmp.cmp(os.path.join(d1, f"{name}.csv"), os.path.join(d2, f"{name}.csv"), shallow=False), name
 
 
-def _claimer(qdir, n_batches, out_path, delay):
+def _claimer(qdir, n_batches, out_path, delay, start):
     import time as _t
     a = argparse.Namespace(queue=qdir, world=3, rank=0, batch=4)
     table = pd.DataFrame({"x": range(4 * n_batches - 1)})  # last batch short
     got = []
+    start.wait(timeout=120)  # claim only once every process is up (their imports take unequal time)
     for rows in plate.batch_source(table, a, 0):
         got.append(rows)
         _t.sleep(delay)
@@ -151,7 +152,8 @@ def test_work_queue_claims_every_batch_once(tmp_path):
     ctx = mp.get_context("spawn")
     n = 23
     outs = [str(tmp_path / f"r{r}.json") for r in range(3)]
-    procs = [ctx.Process(target=_claimer, args=(str(tmp_path / "q"), n, outs[r], d))
+    start = ctx.Barrier(3)
+    procs = [ctx.Process(target=_claimer, args=(str(tmp_path / "q"), n, outs[r], d, start))
              for r, d in enumerate((0.002, 0.002, 0.05))]
     for p in procs:
         p.start()

@@ -10,7 +10,7 @@ BATCH=${BATCH:-48}  # bench.py's default --batch
 PREC=${PREC:-f16x3}  # bench.py's default --cpnet-precision
 mkdir -p $O
 cd $R
-timeout -k 10 420 python -u bench.py > $O/bench_default.log 2>&1
+timeout -k 10 420 python -u bench.py --full > $O/bench_default.log 2>&1
 timeout -k 10 200 python -u tools/flow_error_flops.py > $O/flow_error_flops.json 2> $O/flow_error_flops.log
 cd /tmp && export TMPDIR=/tmp
 cd $R
@@ -18,18 +18,18 @@ cd $R
 # stage timing that the roofline uses); the default two-pipeline run overlaps batches, so its
 # kernel durations include co-resident work (kernels_concurrent.md)
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o run -- \
-  python -u bench.py --pipes 1 --steps 6 --warmup 2 --no-cpu-baseline --stage-steps 1 > $O/bench_kt.log 2>&1
+  python -u bench.py --pipes 1 --steps 6 --warmup 2 --full --no-cpu-baseline --stage-steps 1 > $O/bench_kt.log 2>&1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt2 -o run -- \
-  python -u bench.py --steps 6 --warmup 2 --no-cpu-baseline --stage-steps 1 > $O/bench_kt2.log 2>&1
+  python -u bench.py --steps 6 --warmup 2 --full --no-cpu-baseline --stage-steps 1 > $O/bench_kt2.log 2>&1
 timeout -s KILL 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/fetch -o run -- \
-  python -u bench.py --pipes 1 --steps 3 --warmup 1 --no-cpu-baseline --stage-steps 1 > $O/bench_fetch.log 2>&1
+  python -u bench.py --pipes 1 --steps 3 --warmup 1 --full --no-cpu-baseline --stage-steps 1 > $O/bench_fetch.log 2>&1
 timeout -s KILL 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/write -o run -- \
-  python -u bench.py --pipes 1 --steps 3 --warmup 1 --no-cpu-baseline --stage-steps 1 > $O/bench_write.log 2>&1
+  python -u bench.py --pipes 1 --steps 3 --warmup 1 --full --no-cpu-baseline --stage-steps 1 > $O/bench_write.log 2>&1
 timeout -s KILL 300 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE --output-format csv -d $O/mfma -o run -- \
-  python -u bench.py --pipes 1 --steps 3 --warmup 1 --no-cpu-baseline --stage-steps 1 > $O/bench_mfma.log 2>&1
+  python -u bench.py --pipes 1 --steps 3 --warmup 1 --full --no-cpu-baseline --stage-steps 1 > $O/bench_mfma.log 2>&1
 # VALU instructions of the register flow-error kernels (bench.py's roofline_all.flow_error_reg)
 timeout -s KILL 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVES --kernel-include-regex k_flow_error_reg --output-format csv \
-  -d $O/sqfe -o run -- python -u bench.py --pipes 1 --steps 3 --warmup 1 --no-cpu-baseline --stage-steps 1 > $O/bench_sqfe.log 2>&1
+  -d $O/sqfe -o run -- python -u bench.py --pipes 1 --steps 3 --warmup 1 --full --no-cpu-baseline --stage-steps 1 > $O/bench_sqfe.log 2>&1
 
 # summarise on the box (raw per-dispatch CSVs are too large to bring back)
 python tools/prof_summary.py $O/kt/run_kernel_trace.csv --steps 4 --md > $O/kernels_steady.md
