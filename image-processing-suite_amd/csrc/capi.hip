@@ -148,6 +148,20 @@ int cpx_debug_seg_stats(cpx_ctx* ctx, double* follow_ms, double* item_steps, dou
   return CPX_OK;
 }
 
+int cpx_debug_flow_error_counts(cpx_ctx* ctx, int out[8]) {
+  CPX_REQUIRE(ctx && out, CPX_ERR_ARG, "cpx_debug_flow_error_counts: null argument");
+  for (int i = 0; i < 8; ++i) out[i] = 0;
+  if (ctx->fe_count_off < 0 || !ctx->ws[WS_SEG_OBJ]) return CPX_OK;
+  int c[8];
+  CPX_CHECK_HIP(hipMemcpyAsync(c, (const unsigned char*)ctx->ws[WS_SEG_OBJ] + ctx->fe_count_off, sizeof(c),
+                               hipMemcpyDeviceToHost, ctx->stream));
+  CPX_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  for (int i = 0; i < kFeLists; ++i) out[i] = c[i];
+  return CPX_OK;
+}
+
+int cpx_debug_flow_error_class(int bh, int bw) { return fe_class(bh, bw); }
+
 int cpx_set_stream(cpx_ctx* ctx, void* hip_stream) {
   CPX_REQUIRE(ctx != nullptr, CPX_ERR_ARG, "cpx_set_stream: ctx is NULL");
   // NULL selects the legacy default stream (torch's default stream handle is 0)

@@ -53,6 +53,9 @@ struct cpx_ctx {
   int seg_cnt_cap[kSegEv] = {};
   int seg_B[kSegEv] = {}, seg_rounds[kSegEv] = {};
   int seg_K[kSegEv][64] = {};         // steps per round
+  // byte offset in WS_SEG_OBJ of the last cpx_seg_masks call's flow-error list counts
+  // (cpx_debug_flow_error_counts); -1: no call yet, or one without the flow-error filter
+  long long fe_count_off = -1;
 };
 
 void cpx_fov_free(cpx_ctx* ctx);
@@ -137,10 +140,70 @@ __device__ __forceinline__ T wave_max(T v) {
 // CPX_SEG_ERR_INTERNAL in every FOV's stats instead of a kernel that never ends.
 constexpr int kClaimBroken = 1 << 30;
 
-// Flow-error register classes (k_flowerr_reg.hip fe_reg_class): every such mask's bbox is within
-// kFeRegMaxLong x kFeRegMaxShort in one orientation or the other (k_seg.hip checks that the fp32
-// screening's largest LDS class holds all of them)
+// ---- flow-error filter: mask classes and work lists (k_seg.hip, k_flowerr_reg.hip) ----------
+// One definition of which kernel takes a mask, shared by the classifier kernel, the kernels and
+// the host (cpx_debug_flow_error_class).
+// Register classes: every such mask's bbox is within kFeRegMaxLong x kFeRegMaxShort in one
+// orientation or the other (the static_assert below: the LDS screening class holds all of them,
+// so the fp64 LDS body can decide any mask the register screening defers)
 constexpr int kFeRegMaxLong = 128, kFeRegMaxShort = 120;
+constexpr int kFeRegRows = 40;   // k_flow_error_reg<.., 2, 2>: register rows per wave
+constexpr int kFeReg1Rows = 80;  // k_flow_error_reg1: register rows of its one wave
+// LDS kernels (k_flow_error_lds): a work unit is kFeKS rows of one column pair, kFeU units per
+// thread; the grid of (bh + 2) rows at stride fe_stride(bw) lives in kFeLargeCells fp64 cells
+// (158 KiB: one 1024-thread block per CU) or as many fp32 cells (79 KiB: two 512-thread blocks)
+constexpr int kFeKS = 12;
+constexpr int kFeU = 1;
+constexpr int kFeLargeThreads = 1024, kFeLargeCells = 20224;
+// the grid's row stride: bw + 2 columns (zero border) rounded up to even, so a column pair
+// (2m, 2m + 1) is one 16-byte LDS word
+__host__ __device__ constexpr int fe_stride(int bw) { return (bw + 3) & ~1; }
+__host__ __device__ constexpr bool fe_fits(int bh, int bw, int threads, int units, int cells) {
+  const int nsr = (bh + kFeKS - 1) / kFeKS;
+  return (long long)(bh + 2) * fe_stride(bw) <= cells &&
+         (long long)((bw + 1) / 2) * nsr <= (long long)threads * units;
+}
+// Which register kernel takes a mask, and its storage orientation (tr: storage rows = original
+// columns).  Class 1 (k_flow_error_reg1): one column per lane, the mask's columns <= 64 lanes and
+// its rows <= kFeReg1Rows registers, rows = the shorter side when both fit.  Class 2
+// (k_flow_error_reg, two columns per lane over two waves): columns <= 128, rows <= 2 x kFeRegRows
+// (80); class 3 the same over four waves, rows <= 3 x kFeRegRows (120); rows = the shorter side.
+// Class 0: the LDS kernels.
+__host__ __device__ constexpr int fe_reg_class(int bh, int bw, bool& tr) {
+  const int mn = bh < bw ? bh : bw, mx = bh < bw ? bw : bh;
+  if (mn < 1) return 0;
+  if (mx <= 64) { tr = bh > bw; return 1; }
+  if (mn <= 64 && mx <= kFeReg1Rows) { tr = bw > bh; return 1; }
+  if (mx <= 128 && mn <= 2 * kFeRegRows) { tr = bh > bw; return 2; }
+  if (mx <= 128 && mn <= 3 * kFeRegRows) { tr = bh > bw; return 3; }
+  return 0;
+}
+// The work lists: k_fe_classify puts every mask on exactly one of the first five (the value of
+// fe_class); the screening kernels append the masks they cannot decide to kFeListUnd, the fp64
+// tail the masks its compact-row body cannot hold to kFeListFallback.  List l is count[l]
+// entries (fov, object) at items + l * cap; cap = B * max_label, so no list can overflow.  The
+// order within a list varies from run to run; no flag depends on it.
+enum { kFeListReg1 = 0, kFeListReg2, kFeListReg3, kFeListLds, kFeListOver, kFeListUnd, kFeListFallback, kFeLists };
+struct cpx_fe_lists {
+  int* count;  // [8]
+  int2* items;
+  long long cap;
+  __device__ __forceinline__ int n(int l) const { return count[l]; }
+  __device__ __forceinline__ int2 at(int l, int i) const { return items[l * cap + i]; }
+  __device__ __forceinline__ void push(int l, int fov, int kobj) const {
+    items[l * cap + atomicAdd(&count[l], 1)] = make_int2(fov, kobj);
+  }
+};
+__host__ __device__ constexpr int fe_class(int bh, int bw) {
+  bool tr = false;
+  const int c = fe_reg_class(bh, bw, tr);
+  if (c) return kFeListReg1 + c - 1;
+  return fe_fits(bh, bw, kFeLargeThreads / 2, 2 * kFeU, kFeLargeCells) ? kFeListLds : kFeListOver;
+}
+static_assert(fe_class(kFeRegMaxLong, kFeRegMaxShort) == kFeListReg3 &&
+                  fe_fits(kFeRegMaxLong, kFeRegMaxShort, kFeLargeThreads / 2, 2 * kFeU, kFeLargeCells) &&
+                  fe_fits(kFeRegMaxShort, kFeRegMaxLong, kFeLargeThreads / 2, 2 * kFeU, kFeLargeCells),
+              "register-class masks must fit the LDS screening class");
 
 // Objects handled by the LDS fast paths in k_texture.hip; the rest go to the k_features.hip
 // fallback kernels (the two predicates must agree between the translation units).
@@ -160,12 +223,12 @@ struct cpx_fallback_lists {
 // Fallback launcher cpx_features_fast calls on its stream once the lists exist.
 typedef int (*cpx_fallback_fn)(cpx_ctx* ctx, hipStream_t stream, const cpx_fallback_lists& fb,
                                void* arg);
-// register-resident fp32 flow-error screening (k_flowerr_reg.hip): flags the masks it decides in
-// bad[] (and lists the undecided ones in und) before the LDS screening kernels of cpx_seg_masks;
-// uses the queue counters ctr[0 .. 2] (zeroed by the caller)
+// register-resident fp32 flow-error screening (k_flowerr_reg.hip): flags the masks of the lists
+// kFeListReg1 .. 3 that it decides in bad[] (and appends the others to kFeListUnd) before the
+// LDS screening kernel of cpx_seg_masks; uses the queue counters ctr[0 .. 2] (zeroed by the caller)
 int cpx_flow_error_reg_launch(int n_cu, hipStream_t stream, const int* m0, const float2* dpf, int Dy, int Dx,
-                              int B, int ML, const cpx_object* obj, const int* off, int* ctr, double thr,
-                              unsigned char* bad, int* und);
+                              int ML, const cpx_object* obj, cpx_fe_lists lists, int* ctr, double thr,
+                              unsigned char* bad);
 int cpx_features_fast(cpx_ctx* ctx, const int32_t* labels_dev, const float* corr_dev, int B, int C,
                       int H, int W, int max_label, int F, const cpx_object* objects_dev,
                       const cpx_fov_objects* hdr_dev, double* feats_dev, cpx_fallback_lists* fb,

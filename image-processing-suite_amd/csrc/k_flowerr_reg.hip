@@ -4,8 +4,8 @@
 // screening pass (k_seg.hip, k_flow_error_lds<..., float>) decides a mask's flag in fp32 only where
 // a certified bound puts its error clearly on one side of the threshold and defers the rest to the
 // fp64 kernels.  The kernels here run the same screening with the grid in VGPRs instead of LDS for
-// masks up to 128 x 120 px (fe_reg_class); they are launched first, and the LDS screening kernels skip every mask
-// whose flag they set.  Compiled with -fno-slp-vectorize: pairing rows into packed adds would
+// masks up to 128 x 120 px (cpx_internal.h fe_reg_class); each claims the masks of its own work
+// list (k_seg.hip k_fe_classify), so no other kernel sees them unless they are deferred.  Compiled with -fno-slp-vectorize: pairing rows into packed adds would
 // separate the DPP neighbour reads from the adds they fold into.
 #include "cpx_internal.h"
 #include <math.h>
@@ -30,8 +30,7 @@ namespace {
 // (Wt: the mask and the 1/9 in one packed multiply).  The summation order differs from the
 // reference's (screening only: every cell still passes through <= 6 roundings of non-negative
 // terms per sweep, within the 11u of the bound k_flow_error_lds certifies); decisions, the
-// `und` list and the bad flags are exactly k_flow_error_lds<..., float>'s, and a mask handled
-// here is skipped by the LDS screening kernels (its flag is already set).
+// undecided list (kFeListUnd) and the bad flags are exactly k_flow_error_lds<..., float>'s.
 __device__ __forceinline__ float dpp_from_left(float v) {  // lane l gets lane l - 1's v (lane 0: 0)
   return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0x138, 0xf, 0xf, true));
 }
@@ -62,7 +61,6 @@ __device__ __forceinline__ int fe_hist_rank(const int* h, int len, long long k) 
   return c0 > k ? 3 * lb : c1 > k ? 3 * lb + 1 : 3 * lb + 2;
 }
 
-constexpr int kFeRegRows = 40;  // register rows per wave (T + Wt: 4 VGPRs per row)
 static_assert(3 * kFeRegRows == kFeRegMaxShort && 2 * 64 == kFeRegMaxLong, "cpx_internal.h class bounds");
 typedef float fe_v2 __attribute__((ext_vector_type(2)));  // v_pk_*_f32 operands
 
@@ -86,34 +84,18 @@ __device__ __forceinline__ void fe_row_op(V* T, int jc, V& v) {
   }
 }
 
-// Which register kernel takes a mask, and its storage orientation (tr: storage rows = original
-// columns).  Class 1 (k_flow_error_reg1): one column per lane, the mask's columns <= 64 lanes and
-// its rows <= kFeReg1Rows registers, rows = the shorter side when both fit.  Class 2
-// (k_flow_error_reg, two columns per lane over two waves): columns <= 128, rows <= 2 x kFeRegRows
-// (80); class 3 the same over four waves of kFeReg3Rows, rows <= 3 x kFeRegRows (120); rows = the
-// shorter side.
-// Class 0: the LDS kernels.
-constexpr int kFeReg1Rows = 80;
-// class 3 runs as four waves of 32 rows: two 256-thread blocks per CU at the kernel's two waves
-// per SIMD fill all eight wave slots, where three waves of 40 rows left two idle (3.27 -> 2.82 ms
+// class 3 (cpx_internal.h fe_reg_class) runs as four waves of 32 rows: two 256-thread blocks per
+// CU at the kernel's two waves per SIMD fill all eight wave slots, where three waves of 40 rows
+// left two idle (3.27 -> 2.82 ms
 // per 32 FOVs, `gpurun_out/r06ag`; five waves of 24 rows or eight of 16 fit fewer waves per CU)
 constexpr int kFeReg3Rows = 32;
 static_assert(4 * kFeReg3Rows >= kFeRegMaxShort, "class 3 rows fit four waves");
-__device__ __forceinline__ int fe_reg_class(int bh, int bw, bool& tr) {
-  const int mn = min(bh, bw), mx = max(bh, bw);
-  if (mn < 1) return 0;
-  if (mx <= 64) { tr = bh > bw; return 1; }
-  if (mn <= 64 && mx <= kFeReg1Rows) { tr = bw > bh; return 1; }
-  if (mx <= 128 && mn <= 2 * kFeRegRows) { tr = bh > bw; return 2; }
-  if (mx <= 128 && mn <= 3 * kFeRegRows) { tr = bh > bw; return 3; }
-  return 0;
-}
 
 template <int RW, int NW, int CLS>
 __global__ __launch_bounds__(64 * NW, 2) void k_flow_error_reg(
-    const int* __restrict__ m0, const float2* __restrict__ dpf, int Dy, int Dx, int B, int max_label,
-    const cpx_object* __restrict__ objects, const int* __restrict__ off, int* __restrict__ ctr, int lo_rows,
-    double thr, unsigned char* __restrict__ bad, int* __restrict__ und) {
+    const int* __restrict__ m0, const float2* __restrict__ dpf, int Dy, int Dx, int max_label,
+    const cpx_object* __restrict__ objects, cpx_fe_lists lists, int* __restrict__ ctr, double thr,
+    unsigned char* __restrict__ bad) {
   static_assert(RW % 8 == 0, "rows in groups of 8");
   constexpr int NT = 64 * NW;
   __shared__ fe_v2 xr[2][NW][2][64];  // boundary rows: [sweep parity][wave][first, last][lane]
@@ -123,7 +105,8 @@ __global__ __launch_bounds__(64 * NW, 2) void k_flow_error_reg(
   __shared__ int sitem, smed2[2];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const long long n = (long long)Dy * Dx;
-  const int total = off[B];
+  constexpr int kList = kFeListReg1 + CLS - 1;  // this kernel's own masks
+  const int total = lists.n(kList);
   for (int claims = 0;; ++claims) {
     if (claims > total) {  // broken claim (cpx_internal.h kClaimBroken)
       if (tid == 0) atomicOr(ctr, kClaimBroken);
@@ -134,15 +117,14 @@ __global__ __launch_bounds__(64 * NW, 2) void k_flow_error_reg(
     const int item = __builtin_amdgcn_readfirstlane(sitem);  // uniform control flow from here
     __syncthreads();
     if (item >= total) break;
-    int fov = 0;
-    while (fov + 1 < B && off[fov + 1] <= item) ++fov;
-    const int kobj = item - off[fov];
+    const int2 code = lists.at(kList, item);
+    const int fov = code.x, kobj = code.y;
     const cpx_object o = objects[(long long)fov * max_label + kobj];
     const int L = o.label;
     const int r0 = o.bbox[0], c0 = o.bbox[1];
     const int bh = o.bbox[2] - r0, bw = o.bbox[3] - c0;
     bool tr = false;
-    if (fe_reg_class(bh, bw, tr) != CLS) continue;  // block-uniform
+    fe_reg_class(bh, bw, tr);  // the list holds class CLS only: the storage orientation
     const int SR = tr ? bw : bh, SC = tr ? bh : bw;  // storage rows / columns
     // rows per wave (the slabs split the mask evenly); this wave's rows 1 + wv RS .. wv RS + nrow
     const int RS = (SR + NW - 1) / NW;
@@ -347,7 +329,7 @@ __global__ __launch_bounds__(64 * NW, 2) void k_flow_error_reg(
       const double err = 0.0 + s0 / (double)o.area + s1 / (double)o.area;
       const double bnd = sb / (double)o.area + 1e-9 * (1.0 + err);
       const unsigned char v = err - thr > bnd ? 1 : thr - err > bnd ? 2 : 3;
-      if (v == 3) und[1 + atomicAdd(&und[0], 1)] = (fov << 20) | kobj;
+      if (v == 3) lists.push(kFeListUnd, fov, kobj);
       bad[(long long)fov * (max_label + 1) + L] = v;
     }
     __syncthreads();
@@ -362,14 +344,14 @@ __global__ __launch_bounds__(64 * NW, 2) void k_flow_error_reg(
 // and decision as k_flow_error_reg.
 template <int RW>
 __global__ __launch_bounds__(64, 2) void k_flow_error_reg1(
-    const int* __restrict__ m0, const float2* __restrict__ dpf, int Dy, int Dx, int B, int max_label,
-    const cpx_object* __restrict__ objects, const int* __restrict__ off, int* __restrict__ ctr, double thr,
-    unsigned char* __restrict__ bad, int* __restrict__ und) {
+    const int* __restrict__ m0, const float2* __restrict__ dpf, int Dy, int Dx, int max_label,
+    const cpx_object* __restrict__ objects, cpx_fe_lists lists, int* __restrict__ ctr, double thr,
+    unsigned char* __restrict__ bad) {
   static_assert(RW % 8 == 0, "rows in groups of 8");
   __shared__ int hrow[RW], hcol[64];
   const int lane = threadIdx.x;
   const long long n = (long long)Dy * Dx;
-  const int total = off[B];
+  const int total = lists.n(kFeListReg1);
   for (int claims = 0;; ++claims) {
     if (claims > total) {  // broken claim (cpx_internal.h kClaimBroken); claims is wave-uniform
       if (lane == 0) atomicOr(ctr, kClaimBroken);
@@ -381,15 +363,14 @@ __global__ __launch_bounds__(64, 2) void k_flow_error_reg1(
     // shared item without re-claiming and the loop never ended
     const int item = __builtin_amdgcn_readfirstlane(atomicAdd(ctr, lane == 0 ? 1 : 0));
     if (item >= total) break;
-    int fov = 0;
-    while (fov + 1 < B && off[fov + 1] <= item) ++fov;
-    const int kobj = item - off[fov];
+    const int2 code = lists.at(kFeListReg1, item);
+    const int fov = code.x, kobj = code.y;
     const cpx_object o = objects[(long long)fov * max_label + kobj];
     const int L = o.label;
     const int r0 = o.bbox[0], c0 = o.bbox[1];
     const int bh = o.bbox[2] - r0, bw = o.bbox[3] - c0;
     bool tr = false;
-    if (fe_reg_class(bh, bw, tr) != 1) continue;  // wave-uniform
+    fe_reg_class(bh, bw, tr);  // the list holds class 1 only: the storage orientation
     const int SR = __builtin_amdgcn_readfirstlane(tr ? bw : bh), SC = tr ? bh : bw;  // storage rows / columns
     const int* lab = m0 + (long long)fov * n + (long long)r0 * Dx + c0;
     hcol[lane] = 0;
@@ -530,7 +511,7 @@ __global__ __launch_bounds__(64, 2) void k_flow_error_reg1(
       const double err = 0.0 + e0 / (double)o.area + e1 / (double)o.area;
       const double bnd = eb / (double)o.area + 1e-9 * (1.0 + err);
       const unsigned char v = err - thr > bnd ? 1 : thr - err > bnd ? 2 : 3;
-      if (v == 3) und[1 + atomicAdd(&und[0], 1)] = (fov << 20) | kobj;
+      if (v == 3) lists.push(kFeListUnd, fov, kobj);
       bad[(long long)fov * (max_label + 1) + L] = v;
     }
   }
@@ -540,14 +521,14 @@ __global__ __launch_bounds__(64, 2) void k_flow_error_reg1(
 }  // namespace
 
 int cpx_flow_error_reg_launch(int n_cu, hipStream_t stream, const int* m0, const float2* dpf, int Dy, int Dx,
-                              int B, int ML, const cpx_object* obj, const int* off, int* ctr, double thr,
-                              unsigned char* bad, int* und) {
-  hipLaunchKernelGGL((k_flow_error_reg1<kFeReg1Rows>), dim3(8 * n_cu), dim3(64), 0, stream, m0, dpf, Dy, Dx, B,
-                     ML, obj, off, ctr, thr, bad, und);
+                              int ML, const cpx_object* obj, cpx_fe_lists lists, int* ctr, double thr,
+                              unsigned char* bad) {
+  hipLaunchKernelGGL((k_flow_error_reg1<kFeReg1Rows>), dim3(8 * n_cu), dim3(64), 0, stream, m0, dpf, Dy, Dx,
+                     ML, obj, lists, ctr, thr, bad);
   hipLaunchKernelGGL((k_flow_error_reg<kFeRegRows, 2, 2>), dim3(4 * n_cu), dim3(128), 0, stream, m0, dpf, Dy, Dx,
-                     B, ML, obj, off, ctr + 1, 0, thr, bad, und);
+                     ML, obj, lists, ctr + 1, thr, bad);
   hipLaunchKernelGGL((k_flow_error_reg<kFeReg3Rows, 4, 3>), dim3(2 * n_cu), dim3(256), 0, stream, m0, dpf, Dy, Dx,
-                     B, ML, obj, off, ctr + 2, 0, thr, bad, und);
+                     ML, obj, lists, ctr + 2, thr, bad);
   CPX_CHECK_LAUNCH("k_flow_error_reg");
   return CPX_OK;
 }

@@ -985,7 +985,9 @@ __global__ __launch_bounds__(kT) void k_apply_newlab(int Dy, int Dx, DynBufs d) 
 // masks_to_flows heat diffusion from the pixel nearest the median, 2 * (ptp x + ptp y) Jacobi
 // iterations in fp64, normalised central differences, mean squared difference to dP / 5.
 //
-// k_flow_error_lds: one block per mask (dynamic queue over all masks of the batch).  The
+// k_fe_classify puts every mask on the work list of its class (cpx_internal.h fe_class); every
+// kernel below claims the masks of its own list only.
+// fe_lds_mask (k_flow_error_lds, k_flow_error_tail): one block per mask (dynamic queue).  The
 // diffusion grid T ((bh+2) x (bw+2) fp64 at an even row stride, zero outside the mask) lives in
 // LDS as ONE buffer: a work unit is kFeKS consecutive rows of two adjacent columns (X, X + 1),
 // X odd; the thread that owns it slides a 3 x 4 window down the unit (two 16-byte LDS reads per
@@ -1020,27 +1022,28 @@ __device__ __forceinline__ void fe_pair(const E2& ua, const E2& ub, const E2& ca
   n1 = (E)(1 / 9.) * s1;  // column X + 1
 }
 
-constexpr int kFeKS = 12;
 static_assert(kFeKS <= 32, "unit mask bits");
 
-// the grid's row stride: bw + 2 columns (zero border) rounded up to even, so a column pair
-// (2m, 2m + 1) is one 16-byte LDS word
-__host__ __device__ constexpr int fe_stride(int bw) { return (bw + 3) & ~1; }
-__host__ __device__ constexpr bool fe_fits(int bh, int bw, int threads, int units, int cells) {
-  const int nsr = (bh + kFeKS - 1) / kFeKS;
-  return (long long)(bh + 2) * fe_stride(bw) <= cells &&
-         (long long)((bw + 1) / 2) * nsr <= (long long)threads * units;
-}
-
-// exclusive prefix of the per-FOV object counts (queue item -> (fov, object))
-__global__ void k_obj_prefix(int B, const cpx_fov_objects* __restrict__ hdr, int* __restrict__ off) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
-    int s = 0;
-    for (int b = 0; b < B; ++b) {
-      off[b] = s;
-      s += hdr[b].n_objects;
-    }
-    off[B] = s;
+// every mask of the batch onto the work list of its class (cpx_internal.h fe_class): one thread
+// per (fov, object), so each flow-error kernel claims only its own masks
+__global__ __launch_bounds__(256) void k_fe_classify(int max_label, const cpx_object* __restrict__ objects,
+                                                     const cpx_fov_objects* __restrict__ hdr,
+                                                     cpx_fe_lists lists) {
+  const int fov = blockIdx.y, k = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
+  int cls = -1;
+  if (k < min(hdr[fov].n_objects, max_label)) {
+    const cpx_object& o = objects[(long long)fov * max_label + k];
+    cls = fe_class(o.bbox[2] - o.bbox[0], o.bbox[3] - o.bbox[1]);
+  }
+  // one atomic per wave and list (every mask of the batch lands on five addresses)
+  for (int c = kFeListReg1; c <= kFeListOver; ++c) {
+    const unsigned long long b = __ballot(cls == c);
+    if (!b) continue;  // wave-uniform
+    const int lead = __ffsll((long long)b) - 1;
+    int base = 0;
+    if (lane == lead) base = atomicAdd(&lists.count[c], __popcll(b));
+    base = __shfl(base, lead, 64);
+    if (cls == c) lists.items[c * lists.cap + base + __popcll(b & ((1ull << lane) - 1ull))] = make_int2(fov, k);
   }
 }
 
@@ -1053,52 +1056,35 @@ __global__ void k_obj_prefix(int B, const cpx_fov_objects* __restrict__ hdr, int
 // pixel whose gradient is not clearly above its own uncertainty counts its whole range
 // (1 + |dP/5|)^2).  A mask whose fp32 error is further from thr than the summed bound gets its
 // flag (1 bad, 2 kept) — the same flag the fp64 sweeps give it; any other mask is flagged 3 and
-// appended to `und` ([0] = count, then fov << 20 | object), which the fp64 pass (list = und)
-// then decides exactly.
-template <int THREADS, int CELLS, int U, typename E = double, int WPE = 4>
-__global__ __launch_bounds__(THREADS, WPE) void k_flow_error_lds(  // WPE waves per SIMD: <= 512 / WPE VGPRs
-    const int* __restrict__ m0, const float2* __restrict__ dpf, int Dy, int Dx, int B, int max_label,
-    const cpx_object* __restrict__ objects, const int* __restrict__ off, int* __restrict__ ctr,
-    int lo_threads, int lo_units, int lo_cells, double thr, unsigned char* __restrict__ bad,
-    const int* __restrict__ list, int* __restrict__ und) {
+// appended to the list kFeListUnd, which the fp64 tail (k_flow_error_tail) then decides exactly.
+//
+// fe_lds_mask is one mask's work by a whole block (every thread reaches every barrier in it);
+// T holds (bh + 2) * fe_stride(bw) cells, which the mask's list guarantees (fe_class).
+template <int THREADS>
+struct FeShared {  // the per-block scratch of the LDS bodies beside the grid
+  double sred[THREADS / 64][3];
+  unsigned long long sbest[THREADS / 64];
+  double smed[2];
+  int sitem, stot;
+};
+
+template <int THREADS, int U, typename E>
+__device__ __forceinline__ void fe_lds_mask(E* T, FeShared<THREADS>& sh, const int* __restrict__ m0,
+                                            const float2* __restrict__ dpf, int Dy, int Dx, int max_label,
+                                            const cpx_object* __restrict__ objects, const cpx_fe_lists& lists,
+                                            int fov, int kobj, double thr, unsigned char* __restrict__ bad) {
   constexpr bool kScreen = std::is_same<E, float>::value;
   typedef typename std::conditional<kScreen, float2, double2>::type E2;
-  __shared__ __attribute__((aligned(16))) E T[CELLS];
-  __shared__ double sred[THREADS / 64][3];
-  __shared__ unsigned long long sbest[THREADS / 64];
-  __shared__ double smed[2];
-  __shared__ int sitem;
+  auto& sred = sh.sred;
+  auto& sbest = sh.sbest;
+  auto& smed = sh.smed;
   const long long n = (long long)Dy * Dx;
-  const int total = list ? list[0] : off[B];
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  for (int claims = 0;; ++claims) {
-    if (claims > total) {  // broken claim (cpx_internal.h kClaimBroken)
-      if (tid == 0) atomicOr(ctr, kClaimBroken);
-      break;
-    }
-    if (tid == 0) sitem = atomicAdd(ctr, 1);
-    __syncthreads();
-    const int item = sitem;
-    __syncthreads();
-    if (item >= total) break;
-    int fov = 0, kobj;
-    if (list) {  // the screening pass's undecided masks
-      const int code = list[1 + item];
-      fov = code >> 20;
-      kobj = code & 0xfffff;
-    } else {
-      while (fov + 1 < B && off[fov + 1] <= item) ++fov;
-      kobj = item - off[fov];
-    }
+  {
     const cpx_object o = objects[(long long)fov * max_label + kobj];
     const int L = o.label;
     const int r0 = o.bbox[0], c0 = o.bbox[1];
     const int bh = o.bbox[2] - r0, bw = o.bbox[3] - c0;
-    // block-uniform: objects of the smaller variant or of k_flow_error_big are skipped
-    if (!fe_fits(bh, bw, THREADS, U, CELLS)) continue;
-    if (lo_threads > 0 && fe_fits(bh, bw, lo_threads, lo_units, lo_cells)) continue;
-    // screening: masks k_flow_error_reg already decided (or deferred) carry their flag
-    if (kScreen && !list && bad[(long long)fov * (max_label + 1) + L] != 0) continue;
     // rows per unit: the one-block-per-CU variant (latency-bound: one mask at a time) takes the
     // fewest (<= kFeKS) that keep the units within the block, so a mask spreads over more lanes
     // with shorter per-iteration chains; the multi-block variants keep kFeKS (throughput-bound:
@@ -1327,7 +1313,7 @@ __global__ __launch_bounds__(THREADS, WPE) void k_flow_error_lds(  // WPE waves 
         // + the two fp64 error sums' own rounding (orders differ) with a wide margin
         const double bnd = sb / (double)o.area + 1e-9 * (1.0 + err);
         v = err - thr > bnd ? 1 : thr - err > bnd ? 2 : 3;
-        if (v == 3) und[1 + atomicAdd(&und[0], 1)] = (fov << 20) | kobj;
+        if (v == 3) lists.push(kFeListUnd, fov, kobj);
       }
       bad[(long long)fov * (max_label + 1) + L] = v;
     }
@@ -1335,51 +1321,64 @@ __global__ __launch_bounds__(THREADS, WPE) void k_flow_error_lds(  // WPE waves 
   }
 }
 
-// k_flow_error_cmp: the same per-mask diffusion for masks whose full (bh + 2) x stride grid does
-// not fit the large LDS kernel (kFeLargeCells; its per-row span lookups make it slower there): T holds only each row's span of mask cells (row y keeps the
-// column pairs [pb, pe] covering its mask pixels, at T2[base + p]); every cell outside a row's
-// span is a non-mask cell of the reference's grid, which stays 0.0 for the whole diffusion, so
-// reads there return zero.  Round masks keep ~80 % of their bbox, which takes masks up to about
-// 155 x 155 px in one CU.  One unit (2 columns x kFeKS rows) per thread; masks with more units,
-// more than kCmpRows rows or more cells are left to k_flow_error_big (their flag stays 0).
-constexpr int kCmpRows = 256;
-
-template <int THREADS, int CELLS, int U>
-__global__ __launch_bounds__(THREADS, 1) void k_flow_error_cmp(
-    const int* __restrict__ m0, const float2* __restrict__ dpf, int Dy, int Dx, int B, int max_label,
-    const cpx_object* __restrict__ objects, const int* __restrict__ off, int* __restrict__ ctr,
-    int lo_threads, int lo_units, int lo_cells, double thr, unsigned char* __restrict__ bad) {
-  __shared__ __attribute__((aligned(16))) double T[CELLS];
-  __shared__ int2 rowt[kCmpRows + 2];  // (base, pb | pe << 16) per T row; empty: pb 1, pe 0
-  __shared__ double sred[THREADS / 64][2];
-  __shared__ unsigned long long sbest[THREADS / 64];
-  __shared__ double smed[2];
-  __shared__ int sitem, stot;
-  const long long n = (long long)Dy * Dx;
-  const int total = off[B];
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const double2 z2 = {0.0, 0.0};
+// the fp32 screening of the list kFeListLds: one block per mask (dynamic queue over the list)
+template <int THREADS, int CELLS, int U, typename E, int WPE>
+__global__ __launch_bounds__(THREADS, WPE) void k_flow_error_lds(  // WPE waves per SIMD: <= 512 / WPE VGPRs
+    const int* __restrict__ m0, const float2* __restrict__ dpf, int Dy, int Dx, int max_label,
+    const cpx_object* __restrict__ objects, cpx_fe_lists lists, int* __restrict__ ctr, double thr,
+    unsigned char* __restrict__ bad) {
+  static_assert(CELLS >= kFeLargeCells && THREADS * U >= kFeLargeThreads / 2 * 2 * kFeU, "holds every mask of kFeListLds");
+  __shared__ __attribute__((aligned(16))) E T[CELLS];
+  __shared__ FeShared<THREADS> sh;
+  const int total = lists.n(kFeListLds);
+  const int tid = threadIdx.x;
   for (int claims = 0;; ++claims) {
     if (claims > total) {  // broken claim (cpx_internal.h kClaimBroken)
       if (tid == 0) atomicOr(ctr, kClaimBroken);
       break;
     }
-    if (tid == 0) sitem = atomicAdd(ctr, 1);
+    if (tid == 0) sh.sitem = atomicAdd(ctr, 1);
     __syncthreads();
-    const int item = sitem;
+    const int item = sh.sitem;
     __syncthreads();
     if (item >= total) break;
-    int fov = 0;
-    while (fov + 1 < B && off[fov + 1] <= item) ++fov;
-    const int kobj = item - off[fov];
+    const int2 code = lists.at(kFeListLds, item);
+    fe_lds_mask<THREADS, U, E>(T, sh, m0, dpf, Dy, Dx, max_label, objects, lists, code.x, code.y, thr, bad);
+  }
+}
+
+// fe_cmp_mask: the same per-mask diffusion for masks whose full (bh + 2) x stride grid does not
+// fit the LDS bodies above (kFeLargeCells; its per-row span lookups make it slower there): T holds
+// only each row's span of mask cells (row y keeps the
+// column pairs [pb, pe] covering its mask pixels, at T2[base + p]); every cell outside a row's
+// span is a non-mask cell of the reference's grid, which stays 0.0 for the whole diffusion, so
+// reads there return zero.  Round masks keep ~80 % of their bbox, which takes masks up to about
+// 155 x 155 px in one CU.  One unit (2 columns x kFeKS rows) per thread; masks with more units,
+// more than kCmpRows rows or more cells are left to k_flow_error_big (their flag stays 0).
+// One mask's work by a whole block (every thread reaches every barrier in it); false
+// (block-uniform, no flag written) when the mask is beyond its limits.  rowt: kCmpRows + 2 entries.
+constexpr int kCmpRows = 256;
+
+template <int THREADS, int CELLS, int U>
+__device__ __forceinline__ bool fe_cmp_mask(double* T, int2* rowt, FeShared<THREADS>& sh,
+                                            const int* __restrict__ m0, const float2* __restrict__ dpf, int Dy,
+                                            int Dx, int max_label, const cpx_object* __restrict__ objects, int fov,
+                                            int kobj, double thr, unsigned char* __restrict__ bad) {
+  auto& sred = sh.sred;
+  auto& sbest = sh.sbest;
+  auto& smed = sh.smed;
+  int& stot = sh.stot;
+  const long long n = (long long)Dy * Dx;
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const double2 z2 = {0.0, 0.0};
+  {
     const cpx_object o = objects[(long long)fov * max_label + kobj];
     const int L = o.label;
     const int r0 = o.bbox[0], c0 = o.bbox[1];
     const int bh = o.bbox[2] - r0, bw = o.bbox[3] - c0;
-    // block-uniform: the smaller kernels' masks, and masks beyond this kernel's limits
-    if (fe_fits(bh, bw, lo_threads, lo_units, lo_cells)) continue;
+    // block-uniform: masks beyond this body's limits
     const int ncp = (bw + 1) / 2;
-    if (bh > kCmpRows || (long long)ncp * ((bh + kFeKS - 1) / kFeKS) > (long long)THREADS * U) continue;
+    if (bh > kCmpRows || (long long)ncp * ((bh + kFeKS - 1) / kFeKS) > (long long)THREADS * U) return false;
     const int G = max(1, THREADS * U / ncp);  // row groups the block holds
     const int R = min(kFeKS, (bh + G - 1) / G);  // rows per unit
     const int nsr = (bh + R - 1) / R;
@@ -1438,7 +1437,7 @@ __global__ __launch_bounds__(THREADS, 1) void k_flow_error_cmp(
     }
     __syncthreads();
     const int tot2 = stot;
-    if (2 * tot2 > CELLS) continue;  // block-uniform: left for k_flow_error_big
+    if (2 * tot2 > CELLS) return false;  // block-uniform
     // ---- argmin of (x-xmed)^2 + (y-ymed)^2, first in row-major order on ties
     const double ymed = smed[0], xmed = smed[1];
     unsigned long long best = ~0ull;
@@ -1592,9 +1591,53 @@ __global__ __launch_bounds__(THREADS, 1) void k_flow_error_cmp(
     }
     __syncthreads();
   }
+  return true;
 }
 
-// masks beyond the LDS kernels: one 1024-thread block per mask (dynamic queue over the batch),
+// k_flow_error_tail: the fp64 sweeps of the masks the fp32 screening could not decide (kFeListUnd,
+// fe_lds_mask whatever their size: the block's 1024 lanes spread a small mask over shorter units)
+// and of the masks beyond the LDS screening class (kFeListOver, fe_cmp_mask), side by side in one
+// launch of one block per CU over one queue: the oversize masks (the longest) first.  Both bodies
+// share the grid buffer; the compact rows' spans take its last cells.  A mask fe_cmp_mask cannot
+// hold goes onto kFeListFallback for k_flow_error_big / k_flow_error_fov.
+constexpr int kFeCmpCells = kFeLargeCells - (kCmpRows + 2);  // compact rows: 156 KiB + the row spans
+static_assert(sizeof(int2) == sizeof(double), "row spans in the grid buffer");
+
+__global__ __launch_bounds__(kFeLargeThreads, 4) void k_flow_error_tail(
+    const int* __restrict__ m0, const float2* __restrict__ dpf, int Dy, int Dx, int max_label,
+    const cpx_object* __restrict__ objects, cpx_fe_lists lists, int* __restrict__ ctr, double thr,
+    unsigned char* __restrict__ bad) {
+  __shared__ __attribute__((aligned(16))) double T[kFeLargeCells];
+  __shared__ FeShared<kFeLargeThreads> sh;
+  const int nover = lists.n(kFeListOver);
+  const int total = nover + lists.n(kFeListUnd);
+  const int tid = threadIdx.x;
+  for (int claims = 0;; ++claims) {
+    if (claims > total) {  // broken claim (cpx_internal.h kClaimBroken)
+      if (tid == 0) atomicOr(ctr, kClaimBroken);
+      break;
+    }
+    if (tid == 0) sh.sitem = atomicAdd(ctr, 1);
+    __syncthreads();
+    const int item = sh.sitem;
+    __syncthreads();
+    if (item >= total) break;
+    if (item < nover) {  // block-uniform
+      const int2 code = lists.at(kFeListOver, item);
+      const bool done = fe_cmp_mask<kFeLargeThreads, kFeCmpCells, 1>(
+          T, reinterpret_cast<int2*>(T + kFeCmpCells), sh, m0, dpf, Dy, Dx, max_label, objects, code.x, code.y,
+          thr, bad);
+      if (!done && tid == 0) lists.push(kFeListFallback, code.x, code.y);
+    } else {
+      const int2 code = lists.at(kFeListUnd, item - nover);
+      fe_lds_mask<kFeLargeThreads, kFeU, double>(T, sh, m0, dpf, Dy, Dx, max_label, objects, lists, code.x,
+                                                 code.y, thr, bad);
+    }
+  }
+}
+
+// masks beyond the LDS kernels (kFeListFallback: an empty list on almost every call, and then
+// every block returns at once): one 1024-thread block per mask (dynamic queue over the list),
 // a two-buffer Jacobi over the mask's pixel list in a block-private slice of global scratch
 // (L2-resident for the masks that reach here); the centre's +1 is applied by the thread that
 // writes the centre, so each iteration needs one barrier.  Masks that do not fit a slice (and
@@ -1602,10 +1645,9 @@ __global__ __launch_bounds__(THREADS, 1) void k_flow_error_cmp(
 constexpr int kBigThreads = 1024;
 
 __global__ __launch_bounds__(kBigThreads) void k_flow_error_big(
-    const int* __restrict__ m0, const float2* __restrict__ dpf, int Dy, int Dx, int B, int max_label,
-    const cpx_object* __restrict__ objects, const int* __restrict__ off, int* __restrict__ ctr,
-    int lo_threads, int lo_units, int lo_cells, double thr, double* __restrict__ gscratch,
-    long long slice, unsigned char* __restrict__ bad) {
+    const int* __restrict__ m0, const float2* __restrict__ dpf, int Dy, int Dx, int max_label,
+    const cpx_object* __restrict__ objects, cpx_fe_lists lists, int* __restrict__ ctr, double thr,
+    double* __restrict__ gscratch, long long slice, unsigned char* __restrict__ bad) {
   __shared__ int rowc[2112];
   __shared__ int colc[2112];
   __shared__ double sred[kBigThreads / 64][2];
@@ -1613,7 +1655,8 @@ __global__ __launch_bounds__(kBigThreads) void k_flow_error_big(
   __shared__ double smed[2];
   __shared__ int sitem, snpix;
   const long long n = (long long)Dy * Dx;
-  const int total = off[B];
+  const int total = lists.n(kFeListFallback);
+  if (total == 0) return;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   double* T0 = gscratch + (long long)blockIdx.x * slice;
   for (int claims = 0;; ++claims) {
@@ -1626,15 +1669,12 @@ __global__ __launch_bounds__(kBigThreads) void k_flow_error_big(
     const int item = sitem;
     __syncthreads();
     if (item >= total) break;
-    int fov = 0;
-    while (fov + 1 < B && off[fov + 1] <= item) ++fov;
-    const int kobj = item - off[fov];
+    const int2 code = lists.at(kFeListFallback, item);
+    const int fov = code.x, kobj = code.y;
     const cpx_object o = objects[(long long)fov * max_label + kobj];
     const int L = o.label;
     const int r0 = o.bbox[0], c0 = o.bbox[1];
     const int bh = o.bbox[2] - r0, bw = o.bbox[3] - c0;
-    if (fe_fits(bh, bw, lo_threads, lo_units, lo_cells)) continue;       // the small kernels'
-    if (bad[(long long)fov * (max_label + 1) + L] != 0) continue;        // k_flow_error_cmp's
     const int ly = bh + 2, lx = bw + 2;
     const long long ncell = (long long)ly * lx;
     const int nb = bh * bw;
@@ -1746,14 +1786,14 @@ __global__ __launch_bounds__(kBigThreads) void k_flow_error_big(
   }
 }
 
-// last resort for masks no block slice holds: one block per FOV walks them with a two-buffer
-// Jacobi in the FOV's whole scratch (no two blocks share a scratch area)
+// last resort for masks no block slice holds: one block per FOV walks the masks of its FOV that
+// kFeListFallback still holds unflagged, with a two-buffer Jacobi in the FOV's whole scratch (no
+// two blocks share a scratch area)
 constexpr int kFlowThreads = 256;
 
 __global__ __launch_bounds__(kFlowThreads) void k_flow_error_fov(
     const int* __restrict__ m0, const float2* __restrict__ dpf, int Dy, int Dx, int max_label,
-    const cpx_object* __restrict__ objects, const cpx_fov_objects* __restrict__ hdr, int lds_threads,
-    int lds_units, int lds_cells, double thr, double* __restrict__ gscratch,
+    const cpx_object* __restrict__ objects, cpx_fe_lists lists, double thr, double* __restrict__ gscratch,
     long long gscratch_per_fov, unsigned char* __restrict__ bad) {
   __shared__ int rowc[2048];
   __shared__ int colc[2048];
@@ -1763,14 +1803,15 @@ __global__ __launch_bounds__(kFlowThreads) void k_flow_error_fov(
   const int fov = blockIdx.x;
   const long long n = (long long)Dy * Dx;
   const int* lab = m0 + (long long)fov * n;
-  const int nobj = hdr[fov].n_objects;
-  for (int k = 0; k < nobj; ++k) {
-  const cpx_object o = objects[(long long)fov * max_label + k];
+  const int nfb = lists.n(kFeListFallback);
+  for (int k = 0; k < nfb; ++k) {
+  const int2 code = lists.at(kFeListFallback, k);
+  if (code.x != fov) continue;  // block-uniform
+  const cpx_object o = objects[(long long)fov * max_label + code.y];
   const int L = o.label;
   const int r0 = o.bbox[0], c0 = o.bbox[1];
   const int bh = o.bbox[2] - r0, bw = o.bbox[3] - c0;
-  if (fe_fits(bh, bw, lds_threads, lds_units, lds_cells)) continue;  // block-uniform: an LDS kernel's
-  if (bad[(long long)fov * (max_label + 1) + L] != 0) continue;      // or an earlier kernel's
+  if (bad[(long long)fov * (max_label + 1) + L] != 0) continue;  // block-uniform: k_flow_error_big's
   const int ly = bh + 2, lx = bw + 2;
   const int ncell = ly * lx;
   double* T0 = gscratch + (long long)fov * gscratch_per_fov;
@@ -2459,18 +2500,6 @@ __global__ void k_seed_count(int B, int ms, const int* __restrict__ totals, cpx_
   if (t > ms) atomicOr(&st[fov].overflow, CPX_SEG_OVF_SEEDS);
 }
 
-constexpr int kFeSmallThreads = 256, kFeSmallCells = 5000;    // 40 KiB: 4 blocks per CU
-constexpr int kFeMidThreads = 512, kFeMidCells = 10176;       // 80 KiB: 2 blocks per CU
-constexpr int kFeLargeThreads = 1024, kFeLargeCells = 20224;  // 158 KiB: 1 block per CU
-constexpr int kFeCmpThreads = 1024, kFeCmpU = 1, kFeCmpCells = 19968;  // compact rows: 156 KiB + rows
-constexpr int kFeU = 1;                                        // 2-column x 12-row units per thread
-// every register-class mask (k_flowerr_reg.hip: bbox within 128 x 120 either way) is one the
-// largest fp32 screening class holds, so the LDS screening is what skips it (bad set by the
-// register kernel) and no register-class mask falls to k_flow_error_cmp / k_flow_error_big
-static_assert(fe_fits(kFeRegMaxLong, kFeRegMaxShort, kFeLargeThreads / 2, 2 * kFeU, kFeLargeCells) &&
-                  fe_fits(kFeRegMaxShort, kFeRegMaxLong, kFeLargeThreads / 2, 2 * kFeU, kFeLargeCells),
-              "register-class masks must fit the large screening class");
-
 extern "C" int cpx_seg_masks(cpx_ctx* ctx, const float* yf_dev, int B, const cpx_seg_geom* geom,
                              int H, int W, int niter, double flow_threshold, int min_size,
                              int max_objects, int resample, int32_t* labels_dev,
@@ -2630,12 +2659,15 @@ extern "C" int cpx_seg_masks(cpx_ctx* ctx, const float* yf_dev, int B, const cpx
   const size_t sz_l2i = al(sizeof(int) * (size_t)B * (ML + 1));
   const size_t sz_abs = al(sizeof(int) * (size_t)B * ML);
   const size_t sz_nl = sz_abs;
-  const size_t sz_off = al(sizeof(int) * (size_t)(B + 1 + 11));  // prefix + 11 queue counters
-  const size_t sz_und = al(sizeof(int) * ((size_t)B * ML + 1));  // screening: undecided masks
+  // flow-error work lists (cpx_internal.h cpx_fe_lists): kFeLists counts (padded to 8) and the
+  // kernels' 6 queue counters, then the lists' entries
+  constexpr int kFeQueues = 6;
+  const size_t sz_fec = al(sizeof(int) * (8 + kFeQueues));
+  const size_t sz_fel = al(sizeof(int2) * (size_t)kFeLists * B * ML);
   const size_t gscr_per = (size_t)2 * (Dy + 2) * (Dx + 2);  // doubles per FOV (oversize masks)
   const size_t sz_gscr = al(sizeof(double) * B * gscr_per);
   unsigned char* o = (unsigned char*)cpx_ws(ctx, WS_SEG_OBJ,
-      sz_lst + sz_obj + sz_hdr + sz_bad + sz_l2i + sz_abs + sz_nl + sz_off + sz_und + sz_gscr);
+      sz_lst + sz_obj + sz_hdr + sz_bad + sz_l2i + sz_abs + sz_nl + sz_fec + sz_fel + sz_gscr);
   if (!o) return CPX_ERR_OOM;
   cpx_label_stats* lst = (cpx_label_stats*)o; o += sz_lst;
   cpx_object* obj = (cpx_object*)o; o += sz_obj;
@@ -2644,84 +2676,54 @@ extern "C" int cpx_seg_masks(cpx_ctx* ctx, const float* yf_dev, int B, const cpx
   int* l2i = (int*)o; o += sz_l2i;
   int* absorber = (int*)o; o += sz_abs;
   int* newlab = (int*)o; o += sz_nl;
-  int* off = (int*)o; o += sz_off;
-  int* und = (int*)o; o += sz_und;
+  int* fec = (int*)o; o += sz_fec;
+  int2* fel = (int2*)o; o += sz_fel;
   double* gscr = (double*)o;
+  ctx->fe_count_off = -1;
   if (flow_threshold > 0.0) {
     rc = cpx_objects(ctx, d.m0, B, Dy, Dx, ML, 0, lst, obj, hdr);
     if (rc) return rc;
     CPX_CHECK_HIP(hipMemsetAsync(bad, 0, sz_bad, ctx->stream));
-    CPX_CHECK_HIP(hipMemsetAsync(off + B + 1, 0, 11 * sizeof(int), ctx->stream));
-    CPX_CHECK_HIP(hipMemsetAsync(und, 0, sizeof(int), ctx->stream));
-    hipLaunchKernelGGL(k_obj_prefix, dim3(1), dim3(64), 0, ctx->stream, B,
-                       (const cpx_fov_objects*)hdr, off);
-    // fp32 screening of every mask the LDS kernels hold (half the LDS: twice the masks per CU),
-    // then the fp64 sweeps for the masks it could not decide
-    const int* lst_in = nullptr;
-    if (B < 2048 && ML <= (1 << 20)) {  // list codes: fov << 20 | object
-#define FE_SCREEN(TH, CE, U_, WPE, G, CTR, LT, LU, LC)                                                  \
-  hipLaunchKernelGGL((k_flow_error_lds<TH, CE, U_, float, WPE>), dim3((G) * ctx->n_cu), dim3(TH), 0,    \
-                     ctx->stream, (const int*)d.m0, (const float2*)d.dpf, Dy, Dx, B, ML,             \
-                     (const cpx_object*)obj, (const int*)off, off + B + (CTR), LT, LU, LC, flow_threshold, \
-                     bad, (const int*)nullptr, und)
-      // masks of fe_reg_class 1-3 (k_flowerr_reg.hip: up to 64 x 80 one column per lane, 128 x 80 /
-      // 128 x 120 in column pairs over two / four waves)
-      // first, in VGPRs (k_flow_error_reg); the LDS kernels skip the masks those flagged
-      if (sev >= 0) CPX_CHECK_HIP(hipEventRecord(ctx->seg_ev[sev][2], ctx->stream));
-      rc = cpx_flow_error_reg_launch(ctx->n_cu, ctx->stream, d.m0, (const float2*)d.dpf, Dy, Dx, B, ML,
-                                     obj, off, off + B + 9, flow_threshold, bad, und);
-      if (rc) return rc;
-      if (sev >= 0) {
-        CPX_CHECK_HIP(hipEventRecord(ctx->seg_ev[sev][3], ctx->stream));
-        fe_timed = true;
-      }
-      // six waves per SIMD for the small and mid classes; the large class as 512 threads with two
-      // units each (the same masks as the fp64 1024 x 1 kernel), two 79 KiB blocks per CU
-      FE_SCREEN(kFeSmallThreads, kFeSmallCells, kFeU, 6, 6, 6, 0, 0, 0);
-      FE_SCREEN(kFeMidThreads, kFeMidCells, kFeU, 6, 3, 7, kFeSmallThreads, kFeU, kFeSmallCells);
-      FE_SCREEN(kFeLargeThreads / 2, kFeLargeCells, 2 * kFeU, 4, 2, 8, kFeMidThreads, kFeU, kFeMidCells);
-#undef FE_SCREEN
-      lst_in = und;
-      if (getenv("CPX_FE_DEBUG")) {  // profiling aid: masks the screening left undecided
-        int nu = 0, nm = 0;
-        CPX_CHECK_HIP(hipMemcpyAsync(&nu, und, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        CPX_CHECK_HIP(hipMemcpyAsync(&nm, off + B, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-        CPX_CHECK_HIP(hipStreamSynchronize(ctx->stream));
-        fprintf(stderr, "flow error: %d of %d masks undecided by the fp32 screening\n", nu, nm);
-      }
+    CPX_CHECK_HIP(hipMemsetAsync(fec, 0, sizeof(int) * (8 + kFeQueues), ctx->stream));
+    const cpx_fe_lists lists = {fec, fel, (long long)B * ML};
+    int* const fq = fec + 8;  // queue counters: reg1, reg2, reg3, LDS screening, tail, big
+    ctx->fe_count_off = (unsigned char*)fec - (unsigned char*)ctx->ws[WS_SEG_OBJ];
+    hipLaunchKernelGGL(k_fe_classify, dim3(cpx_div_up(ML, 256), B), dim3(256), 0, ctx->stream, ML,
+                       (const cpx_object*)obj, (const cpx_fov_objects*)hdr, lists);
+    // fp32 screening first — masks of fe_reg_class 1-3 in VGPRs (k_flowerr_reg.hip: up to 64 x 80
+    // one column per lane, 128 x 80 / 128 x 120 in column pairs over two / four waves), the other
+    // masks the LDS holds in one launch of the large configuration (512 threads with two units
+    // each, two 79 KiB blocks per CU) — then the fp64 sweeps for the masks it could not decide
+    // and the oversize masks
+    if (sev >= 0) CPX_CHECK_HIP(hipEventRecord(ctx->seg_ev[sev][2], ctx->stream));
+    rc = cpx_flow_error_reg_launch(ctx->n_cu, ctx->stream, d.m0, (const float2*)d.dpf, Dy, Dx, ML, obj, lists,
+                                   fq, flow_threshold, bad);
+    if (rc) return rc;
+    if (sev >= 0) {
+      CPX_CHECK_HIP(hipEventRecord(ctx->seg_ev[sev][3], ctx->stream));
+      fe_timed = true;
     }
-    hipLaunchKernelGGL((k_flow_error_lds<kFeSmallThreads, kFeSmallCells, kFeU>), dim3(4 * ctx->n_cu),
-                       dim3(kFeSmallThreads), 0, ctx->stream, (const int*)d.m0, (const float2*)d.dpf,
-                       Dy, Dx, B, ML, (const cpx_object*)obj, (const int*)off, off + B + 1, 0, 0, 0,
-                       flow_threshold, bad, lst_in, (int*)nullptr);
-    hipLaunchKernelGGL((k_flow_error_lds<kFeMidThreads, kFeMidCells, kFeU>), dim3(2 * ctx->n_cu),
-                       dim3(kFeMidThreads), 0, ctx->stream, (const int*)d.m0, (const float2*)d.dpf,
-                       Dy, Dx, B, ML, (const cpx_object*)obj, (const int*)off, off + B + 2,
-                       kFeSmallThreads, kFeU, kFeSmallCells, flow_threshold, bad, lst_in, (int*)nullptr);
-    hipLaunchKernelGGL((k_flow_error_lds<kFeLargeThreads, kFeLargeCells, kFeU>), dim3(ctx->n_cu),
-                       dim3(kFeLargeThreads), 0, ctx->stream, (const int*)d.m0, (const float2*)d.dpf,
-                       Dy, Dx, B, ML, (const cpx_object*)obj, (const int*)off, off + B + 3,
-                       kFeMidThreads, kFeU, kFeMidCells, flow_threshold, bad, lst_in, (int*)nullptr);
-    hipLaunchKernelGGL((k_flow_error_cmp<kFeCmpThreads, kFeCmpCells, kFeCmpU>), dim3(ctx->n_cu),
-                       dim3(kFeCmpThreads), 0, ctx->stream, (const int*)d.m0, (const float2*)d.dpf,
-                       Dy, Dx, B, ML, (const cpx_object*)obj, (const int*)off, off + B + 4,
-                       kFeLargeThreads, kFeU, kFeLargeCells, flow_threshold, bad);
+    hipLaunchKernelGGL((k_flow_error_lds<kFeLargeThreads / 2, kFeLargeCells, 2 * kFeU, float, 4>),
+                       dim3(2 * ctx->n_cu), dim3(kFeLargeThreads / 2), 0, ctx->stream, (const int*)d.m0,
+                       (const float2*)d.dpf, Dy, Dx, ML, (const cpx_object*)obj, lists, fq + 3, flow_threshold,
+                       bad);
+    hipLaunchKernelGGL(k_flow_error_tail, dim3(ctx->n_cu), dim3(kFeLargeThreads), 0, ctx->stream,
+                       (const int*)d.m0, (const float2*)d.dpf, Dy, Dx, ML, (const cpx_object*)obj, lists,
+                       fq + 4, flow_threshold, bad);
     {
       const int nbig = std::max(1, std::min(ctx->n_cu, 4 * B));
       const long long slice = (long long)(B * gscr_per / nbig) & ~1LL;
       hipLaunchKernelGGL(k_flow_error_big, dim3(nbig), dim3(kBigThreads), 0, ctx->stream,
-                         (const int*)d.m0, (const float2*)d.dpf, Dy, Dx, B, ML, (const cpx_object*)obj,
-                         (const int*)off, off + B + 5, kFeLargeThreads, kFeU, kFeLargeCells, flow_threshold,
-                         gscr, slice, bad);
+                         (const int*)d.m0, (const float2*)d.dpf, Dy, Dx, ML, (const cpx_object*)obj, lists,
+                         fq + 5, flow_threshold, gscr, slice, bad);
     }
     hipLaunchKernelGGL(k_flow_error_fov, dim3(B), dim3(kFlowThreads), 0, ctx->stream,
-                       (const int*)d.m0, (const float2*)d.dpf, Dy, Dx, ML, (const cpx_object*)obj,
-                       (const cpx_fov_objects*)hdr, kFeLargeThreads, kFeU, kFeLargeCells,
+                       (const int*)d.m0, (const float2*)d.dpf, Dy, Dx, ML, (const cpx_object*)obj, lists,
                        flow_threshold, gscr, (long long)gscr_per, bad);
     hipLaunchKernelGGL(k_apply_bad, gp4, dim3(kT), 0, ctx->stream, n, ML,
                        (const unsigned char*)bad, d.m0);
     hipLaunchKernelGGL(k_count_bad, dim3(B), dim3(256), 0, ctx->stream, ML,
-                       (const unsigned char*)bad, (const int*)(off + B + 1), 11, stats_dev);
+                       (const unsigned char*)bad, (const int*)fq, kFeQueues, stats_dev);
     CPX_CHECK_LAUNCH("cpx_seg_masks flow error");
   }
   if (!resample) {

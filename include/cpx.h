@@ -594,6 +594,15 @@ int cpx_debug_glcm_ms(cpx_ctx* ctx, double* ms_out, int* launches_out);
  * bound, an item at an exact fixed point stops early), then resets.                           */
 int cpx_debug_seg_timing(cpx_ctx* ctx, int enable);
 int cpx_debug_seg_stats(cpx_ctx* ctx, double* follow_ms, double* item_steps, double* fe_reg_ms, int* calls);
+/* The flow-error filter's work lists.  cpx_debug_flow_error_class: pure host code, the list the
+ * filter puts a mask with a bh x bw bounding box on — 0, 1, 2 the register kernels' classes 1 - 3,
+ * 3 the fp32 LDS screening, 4 oversize (the compact-row fp64 body).  cpx_debug_flow_error_counts:
+ * the list lengths of the context's last cpx_seg_masks call over its whole batch, out[0 .. 4] as
+ * above, out[5] the masks the fp32 screening left undecided (decided by the fp64 sweeps), out[6]
+ * the oversize masks passed on to the fallback kernels, out[7] = 0; all zero after a call with
+ * flow_threshold <= 0.  It waits for the context's stream (only when called).                  */
+int cpx_debug_flow_error_counts(cpx_ctx* ctx, int out[8]);
+int cpx_debug_flow_error_class(int bh, int bw);
 
 /* ---- host: CSV rows of the measurement tables (Pycyto_pertime.py:46-49 reads them) ------- *
  * Rows [row0, row1) of a table of n_cols columns, column c at cols[c] with element stride
