@@ -8,6 +8,8 @@ writes those four tables from the GPU pipeline's results:
                  ImageQuality_PercentMaximal_<ch>, Count_Nuclei, Count_Cells, Count_Cytoplasm
   <Object>.csv   ImageNumber, ObjectNumber, Number_Object_Number, then the feature columns of
                  `feature_names(channels)` (AreaShape_*, Intensity_*_<ch>, Texture_*_<ch>_3_<dir>_256)
+                 and, with colocalization=True, of `colocalization_names(channels)`
+                 (Correlation_{Correlation,Overlap,Manders,K}_<a>_<b> per channel pair)
 ImageNumber is the 1-based LoadData row; ObjectNumber is the object's label, which the
 segmentation makes consecutive (1..K per image) and which Cells and Cytoplasm share with their
 nucleus.  Rows are sorted by (ImageNumber, ObjectNumber), so the output does not depend on the
@@ -132,6 +134,18 @@ def feature_names(channels):
     return names
 
 
+COLOC_NAMES = ["Correlation_{a}_{b}", "Overlap_{a}_{b}", "Manders_{a}_{b}", "Manders_{b}_{a}",
+               "K_{a}_{b}", "K_{b}_{a}"]
+
+
+def colocalization_names(channels):
+    """Column names of a cpx_colocalization row (include/cpx.h CPX_COLOC_*): six columns per
+    unordered channel pair, the pairs in itertools.combinations order."""
+    import itertools
+    return [f"Correlation_{n.format(a=a, b=b)}" for a, b in itertools.combinations(list(channels), 2)
+            for n in COLOC_NAMES]
+
+
 class _TableStream:
     """Appends formatted CSV blocks to one file on a writer thread, in arrival order, while their
     ImageNumbers increase; finish() reports whether the file is complete and ordered."""
@@ -198,9 +212,12 @@ class _TableStream:
 class PlateTables:
     """Accumulates per-FOV results of one plate/time and writes the four CSVs."""
 
-    def __init__(self, channels, eager_csv: bool = False, stream_dir: str | None = None):
+    def __init__(self, channels, eager_csv: bool = False, stream_dir: str | None = None,
+                 colocalization: bool = False):
         self.channels = list(channels)
         self.cols = feature_names(self.channels)
+        if colocalization:  # rows carry the Correlation_* block after the features (cpx.pipeline)
+            self.cols += colocalization_names(self.channels)
         self.images = []                       # dicts
         self.objects = {t: [] for t in OBJECT_TABLES}  # (ImageNumber, labels[n], feats[n, F])
         # eager_csv: each FOV's object rows are formatted on a thread pool as they are added

@@ -243,6 +243,16 @@ class Device:
                                          *(_ptr(t) for t in cells_tab), *(_ptr(t) for t in cyto_tab)),
               "cpx_features_pair")
 
+    def colocalization(self, labels, corr, C, max_label, objects, hdr, out, threshold: float = 15.0):
+        """cpx_colocalization: out float64 [B, max_label, n_colocalization(C)], row k = the k-th
+        object of the table (rows >= n_objects untouched); threshold in percent of the maximum."""
+        B, H, W = labels.shape
+        assert out.dtype == torch.float64 and out.numel() >= B * max_label * n_colocalization(C)
+        self._bind_stream()
+        check(self.lib.cpx_colocalization(self.h, _ptr(labels), _ptr(corr), B, C, H, W, max_label,
+                                          _ptr(objects), _ptr(hdr), float(threshold), _ptr(out)),
+              "cpx_colocalization")
+
 
 # Pipeline streams with their own CUs (round 5): two pipelines whose streams each hold a CU mask
 # of one contiguous half of the GPU's CUs (hipExtStreamCreateWithCUMask) ran the bench 0.8-0.9 %
@@ -317,6 +327,11 @@ def pipeline_streams(device, n: int, split: str | None = None) -> list:
 
 def n_features(C: int) -> int:
     return _lib.N_SHAPE + C * _lib.FEATURES_PER_CHANNEL
+
+
+def n_colocalization(C: int) -> int:
+    """Columns of a cpx_colocalization row (cpx_n_colocalization): 6 per unordered channel pair."""
+    return _lib.N_COLOC * (C * (C - 1) // 2) if C > 0 else 0
 
 
 def as_numpy(t: torch.Tensor, kind: str):

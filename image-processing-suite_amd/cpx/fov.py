@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check
-from .device import n_features
+from .device import n_colocalization, n_features
 
 
 class FovSession:
@@ -109,6 +109,18 @@ class FovSession:
         n = ct.c_int()
         check(self.lib.cpx_fov_features(self.h, ct.c_void_p(lab.data_ptr()), max_objects,
                                         out.ctypes.data_as(ct.c_void_p), ct.byref(n)), "cpx_fov_features")
+        return out[: n.value].copy()
+
+    def colocalization(self, labels, max_objects: int = 4096, threshold: float = 15.0) -> np.ndarray:
+        """Colocalization rows [n_objects, n_colocalization(C)] of the objects of `labels` over the
+        submitted FOV (the same objects and order as features()); threshold in percent."""
+        lab = self._labels(labels)
+        K = n_colocalization(self.C)
+        out = np.empty((max_objects, K), np.float64)
+        n = ct.c_int()
+        check(self.lib.cpx_fov_colocalization(self.h, ct.c_void_p(lab.data_ptr()), max_objects, float(threshold),
+                                              out.ctypes.data_as(ct.c_void_p), ct.byref(n)),
+              "cpx_fov_colocalization")
         return out[: n.value].copy()
 
     def _labels(self, labels):

@@ -25,7 +25,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .device import Device, as_numpy, n_features
+from ._lib import COLOC_MAX_CHANNELS
+from .device import Device, as_numpy, n_colocalization, n_features
 from .segment import CELLPOSE_MODEL, DIAMETER, Segmenter
 
 OBJECT_SETS = ("Nuclei", "Cells", "Cytoplasm")
@@ -71,6 +72,9 @@ class PipelineConfig:
     crops: bool = False              # a7 crops for the embedding consumer (off in the bench)
     crops_f32: bool = True           # also keep the float crops (the embedder needs only crops8)
     slots: int = 2                   # result buffer sets (fetch of step i overlaps step i + 1)
+    colocalization: bool = False     # also measure the Correlation_* block (cpx_colocalization):
+                                     # FovResults.feats rows get n_colocalization(C) more columns
+    coloc_threshold: float = 15.0    # its threshold, percent of the object's channel maximum
 
     def ws_channel(self) -> int:
         """The watershed elevation channel (cell_channel, or "AGP" / the last channel)."""
@@ -85,7 +89,8 @@ class FovResults:
     qc: np.ndarray                   # structured [B*C] (slope, pct_max, ...)
     hdr: dict                        # set -> structured [B] (n_objects, n_kept, ...)
     objects: dict                    # set -> list of structured arrays (per FOV)
-    feats: dict                      # set -> list of float64 [n_objects, F]
+    feats: dict                      # set -> list of float64 [n_objects, F] (F = n_features(C), plus
+                                     # n_colocalization(C) with PipelineConfig.colocalization)
     seg_stats: np.ndarray
     failed: np.ndarray | None = None  # [B] bool: the FOV's Cells watershed did not converge even
                                       # after the re-runs with more rounds; its object tables are
@@ -146,6 +151,9 @@ class FovPipeline:
         self.labels = {s: torch.empty((B, H, W), dtype=torch.int32, device=td) for s in OBJECT_SETS}
         self.lstats = dev.empty_bytes(64 * B * (ML + 1))
         self.F = n_features(C)
+        if cfg.colocalization and C > COLOC_MAX_CHANNELS:
+            raise ValueError(f"PipelineConfig.colocalization: {C} channels (at most {COLOC_MAX_CHANNELS})")
+        self.K = n_colocalization(C) if cfg.colocalization else 0  # appended columns (0: none)
         self.seg = Segmenter(dev, H, W, B, model=cfg.model, diameter=cfg.diameter, weights=cfg.weights,
                              seed=cfg.seed, use_graph=cfg.use_graph and cfg.cpnet_precision != "fp32",
                              max_objects=ML, resample=cfg.resample, precision=cfg.cpnet_precision)
@@ -160,6 +168,9 @@ class FovPipeline:
                 "seg_stats": torch.empty_like(self.seg.stats),
                 "cpnet_ovf": torch.zeros(max(1, B * self.seg.geom.n_tiles), dtype=torch.int32, device=td),
                 "raw": None, "event": None})
+            if self.K:
+                self._slots[-1]["coloc"] = {s: torch.zeros((B, ML, self.K), dtype=torch.float64, device=td)
+                                            for s in OBJECT_SETS}
         self._host = {
             "qc": torch.empty(24 * B * C, dtype=torch.uint8, pin_memory=True),
             "hdr": {s: torch.empty(16 * B, dtype=torch.uint8, pin_memory=True) for s in OBJECT_SETS},
@@ -167,6 +178,9 @@ class FovPipeline:
             "feats": {s: torch.empty(B * ML * self.F, dtype=torch.float64, pin_memory=True) for s in OBJECT_SETS},
             "seg_stats": torch.empty(self.seg.stats.shape, dtype=self.seg.stats.dtype, pin_memory=True),
             "cpnet_ovf": torch.zeros(max(1, B * self.seg.geom.n_tiles), dtype=torch.int32, pin_memory=True)}
+        if self.K:
+            self._host["coloc"] = {s: torch.empty(B * ML * self.K, dtype=torch.float64, pin_memory=True)
+                                   for s in OBJECT_SETS}
         # one result-copy stream per device, shared by its pipelines: a process has only
         # GPU_MAX_HW_QUEUES (4) hardware queues, and streams beyond that share one, which
         # serialises two pipelines' kernels behind each other
@@ -198,6 +212,7 @@ class FovPipeline:
         sl = self._slots[k]
         self.cur = k
         self.qc, self.hdr, self.objects, self.feats = sl["qc"], sl["hdr"], sl["objects"], sl["feats"]
+        self.coloc = sl.get("coloc")
 
     # ---- stages ---------------------------------------------------------------------------
     # A stage in STAGE_EXCLUSIVE (of illum_qc, cpnet, seg_post, cells, features) of one pipeline
@@ -275,6 +290,10 @@ class FovPipeline:
             for s in ("Cells", "Cytoplasm"):
                 self.dev.features(self.labels[s], self.corr, cfg.C, cfg.max_objects, self.objects[s],
                                   self.hdr[s], self.feats[s])
+        if self.K:
+            for s in OBJECT_SETS:
+                self.dev.colocalization(self.labels[s], self.corr, cfg.C, cfg.max_objects, self.objects[s],
+                                        self.hdr[s], self.coloc[s], cfg.coloc_threshold)
         if self.cfg.crops:
             self.dev.objects(self.labels["Nuclei"], cfg.max_objects, cfg.box, self.lstats,
                              self.objects["Nuclei"], self.hdr["Nuclei"])
@@ -317,7 +336,7 @@ class FovPipeline:
         from .segment import SEG_ERR_INTERNAL, SEG_OVF_FILL_PARTIAL, SEG_OVF_SEEDS, SEG_STATS_DTYPE
         k = self.cur if slot is None else slot
         sl, hb = self._slots[k], self._host
-        B, ML, F = self.cfg.batch, self.cfg.max_objects, self.F
+        B, ML, F, K = self.cfg.batch, self.cfg.max_objects, self.F, self.K
         cs = self._copy_stream
         cs.wait_event(sl["event"])
         with torch.cuda.stream(cs):
@@ -353,6 +372,10 @@ class FovPipeline:
                 hb["feats"][s][:tot * F].view(tot, F).copy_(fg, non_blocking=True)
                 hb["objects"][s][:tot * 56].view(tot, 56).copy_(og, non_blocking=True)
                 keep.append((src, idx, fg, og))
+                if K:
+                    cg = sl["coloc"][s].view(B * ML, K).index_select(0, idx)
+                    hb["coloc"][s][:tot * K].view(tot, K).copy_(cg, non_blocking=True)
+                    keep.append(cg)
         _sync_after(cs)
         del keep
         objs, feats = {}, {}
@@ -361,6 +384,8 @@ class FovPipeline:
             tot = int(n_b.sum())
             off = np.concatenate([[0], np.cumsum(n_b)])
             f = hb["feats"][s][:tot * F].view(tot, F).numpy()
+            if K:  # the Correlation_* block follows the features of each row
+                f = np.concatenate([f, hb["coloc"][s][:tot * K].view(tot, K).numpy()], axis=1)
             o = as_numpy(hb["objects"][s][:max(tot, 1) * 56], "object")[:tot]
             feats[s] = [f[off[b]:off[b + 1]].copy() for b in range(B)]
             objs[s] = [o[off[b]:off[b + 1]].copy() for b in range(B)]

@@ -96,6 +96,12 @@ def parse_args(argv=None):
                     help="with --world > 1: leave the parts for cpx.launch / merge_parts")
     ap.add_argument("--ws-rounds", type=int, nargs=2, default=None, metavar=("RELAX", "LABEL"),
                     help="Cells watershed rounds enqueued per batch (default: PipelineConfig.ws_rounds)")
+    ap.add_argument("--colocalization", action="store_true",
+                    help="also write the per-object Correlation_* columns (Correlation, Overlap, Manders, K per "
+                         "channel pair; PipelineConfig.colocalization) after the feature columns")
+    ap.add_argument("--colocalization-threshold", type=float, default=15.0, metavar="PCT",
+                    help="threshold of the Overlap / Manders / K columns, percent of the object's maximum "
+                         "per channel (default 15)")
     return ap.parse_args(argv)
 
 
@@ -264,7 +270,8 @@ def run(argv=None):
         table, plate, time = _job_meta(a, load_data)
         # one rank: each FOV's rows formatted as it finishes and streamed into the job's CSVs
         out = PlateTables(chans, eager_csv=a.world == 1,
-                          stream_dir=job_dir(a.out, plate, time) if a.world == 1 else None)
+                          stream_dir=job_dir(a.out, plate, time) if a.world == 1 else None,
+                          colocalization=a.colocalization)
         status = []  # per site: the reference's results_dict entry (Cellpose_GPU_s3fs.py:123-125,219-223)
         d = job_dir(a.out, plate, time)
         try:
@@ -354,7 +361,9 @@ def _run_sites(a, table, source, chans, state, out, status):
             weights = cand if os.path.exists(cand) else None
         B = max(1, a.batch)
         cfg = PipelineConfig(H=H, W=W, C=C, batch=B, channels=tuple(chans), weights=weights,
-                             cpnet_precision=getattr(a, "cpnet_precision", "f16x3"))
+                             cpnet_precision=getattr(a, "cpnet_precision", "f16x3"),
+                             colocalization=bool(getattr(a, "colocalization", False)),
+                             coloc_threshold=float(getattr(a, "colocalization_threshold", 15.0)))
         if a.ws_rounds:
             cfg.ws_rounds = tuple(a.ws_rounds)
         illum = _illum(a.illum_path, chans, H, W)

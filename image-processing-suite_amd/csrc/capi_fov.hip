@@ -34,6 +34,8 @@ struct cpx_fov_state {
   int feat_C = 0;
   float* yf = nullptr;
   size_t yf_cap = 0;
+  double* coloc = nullptr;    // [max_objects][cpx_n_colocalization(C)] (cpx_fov_colocalization)
+  size_t coloc_cap = 0;
 };
 
 void cpx_fov_free(cpx_ctx* ctx) {
@@ -42,7 +44,7 @@ void cpx_fov_free(cpx_ctx* ctx) {
   for (void* p : f->illum)
     if (p) (void)hipFree(p);
   void* bufs[] = {f->raw, f->zplane, f->corr, f->stats, f->qc,
-                  f->lstats, f->objects, f->hdr, f->feats, f->yf};
+                  f->lstats, f->objects, f->hdr, f->feats, f->yf, f->coloc};
   for (void* p : bufs)
     if (p) (void)hipFree(p);
   delete f;
@@ -284,6 +286,33 @@ int cpx_fov_features(cpx_ctx* ctx, const int32_t* labels_dev, int max_objects, d
   if (host_out && *n_out > 0) {
     // device rows have the stride of max_objects' table; copy the first n rows (contiguous)
     CPX_CHECK_HIP(hipMemcpyAsync(host_out, f->feats, sizeof(double) * F * (*n_out),
+                                 hipMemcpyDeviceToHost, ctx->stream));
+  }
+  CPX_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  return CPX_OK;
+}
+
+int cpx_fov_colocalization(cpx_ctx* ctx, const int32_t* labels_dev, int max_objects,
+                           double threshold_pct, double* host_out, int* n_out) {
+  CPX_REQUIRE(ctx && labels_dev && n_out && max_objects > 0, CPX_ERR_ARG,
+              "cpx_fov_colocalization: bad argument");
+  CPX_REQUIRE(ctx->fov && ctx->fov->have, CPX_ERR_STATE, "cpx_fov_colocalization: no FOV submitted");
+  cpx_fov_state* f = ctx->fov;
+  CPX_REQUIRE(f->C <= CPX_COLOC_MAX_CHANNELS, CPX_ERR_ARG,
+              "cpx_fov_colocalization: the submitted FOV has %d channels (at most %d supported)", f->C,
+              CPX_COLOC_MAX_CHANNELS);
+  int rc;
+  if ((rc = cpx_fov_object_table(ctx, labels_dev, 0, max_objects, nullptr, n_out)) != CPX_OK) return rc;
+  const size_t K = (size_t)cpx_n_colocalization(f->C);
+  if (K == 0) return CPX_OK;  // one channel: no pair
+  if ((rc = grow(ctx, (void**)&f->coloc, &f->coloc_cap, sizeof(double) * K * max_objects,
+                 "fov colocalization")) != CPX_OK)
+    return rc;
+  if ((rc = cpx_colocalization(ctx, labels_dev, f->corr, 1, f->C, f->H, f->W, max_objects, f->objects,
+                               f->hdr, threshold_pct, f->coloc)) != CPX_OK)
+    return rc;
+  if (host_out && *n_out > 0) {
+    CPX_CHECK_HIP(hipMemcpyAsync(host_out, f->coloc, sizeof(double) * K * (*n_out),
                                  hipMemcpyDeviceToHost, ctx->stream));
   }
   CPX_CHECK_HIP(hipStreamSynchronize(ctx->stream));

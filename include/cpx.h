@@ -294,6 +294,41 @@ int cpx_features_pair(cpx_ctx* ctx, const int32_t* cells_dev, const int32_t* cyt
                       double* cells_feats_dev, const cpx_object* cyto_objects_dev,
                       const cpx_fov_objects* cyto_hdr_dev, double* cyto_feats_dev);
 
+/* ---- a8: per-object colocalization (Correlation_* columns) --------------------------------- *
+ * The cross-channel block a Cell Painting CellProfiler pipeline writes beside AreaShape /
+ * Intensity / Texture in the measurement step of Feature_extraction_opt.py:164-167 (pipeline not
+ * in the reference; the arithmetic of CellProfiler 4's MeasureColocalization object measurements,
+ * restated here and in DESIGN.md §12).  For an object with pixels P (n of them), x_a(p) = the
+ * fp32 corrected plane of channel a widened to float64, mean_a = sum_P x_a / n and
+ * t_a = (threshold_pct / 100.0) * max_P x_a, every unordered channel pair a < b, in
+ * itertools.combinations(range(C), 2) order, has CPX_N_COLOC columns; with
+ * S = {p in P : x_a >= t_a and x_b >= t_b}:
+ *   Correlation  sum_P (x_a - mean_a)(x_b - mean_b) /
+ *                sqrt(sum_P (x_a - mean_a)^2 * sum_P (x_b - mean_b)^2)      (two-pass Pearson)
+ *   Overlap      sum_S x_a x_b / sqrt(sum_S x_a^2 * sum_S x_b^2)
+ *   Manders_AB   sum_S x_a / sum_{p in P, x_a >= t_a} x_a       Manders_BA  the same for b
+ *   K_AB         sum_S x_a x_b / sum_S x_a^2                    K_BA        ... / sum_S x_b^2
+ * Every sum is float64 in a fixed order (two runs give the same bits); every quotient is the plain
+ * IEEE quotient, so 0/0 (a one-pixel object, a constant channel, an empty S) is NaN.           */
+#define CPX_COLOC_CORRELATION 0
+#define CPX_COLOC_OVERLAP 1
+#define CPX_COLOC_MANDERS_AB 2
+#define CPX_COLOC_MANDERS_BA 3
+#define CPX_COLOC_K_AB 4
+#define CPX_COLOC_K_BA 5
+#define CPX_N_COLOC 6
+#define CPX_COLOC_MAX_CHANNELS 8
+/* Columns of a colocalization row: CPX_N_COLOC * C * (C - 1) / 2 (60 for C = 5, 0 for C <= 1). */
+int cpx_n_colocalization(int C);
+/* coloc_dev: float64 [B][max_label][cpx_n_colocalization(C)]; row k is the k-th object of the
+ * FOV's table (objects_dev / hdr_dev as cpx_objects wrote them for labels_dev; rows >= n_objects
+ * untouched).  Each object's bbox is visited, not the plane; an object has no size limit.
+ * threshold_pct within 0 .. 100 (CellProfiler's default: 15).  2 <= C <= CPX_COLOC_MAX_CHANNELS;
+ * C == 1 returns CPX_OK without a launch (no pair, no column), C > 8 is CPX_ERR_ARG.           */
+int cpx_colocalization(cpx_ctx* ctx, const int32_t* labels_dev, const float* corr_dev, int B, int C,
+                       int H, int W, int max_label, const cpx_object* objects_dev,
+                       const cpx_fov_objects* hdr_dev, double threshold_pct, double* coloc_dev);
+
 /* ---- secondary objects for the Cells / Cytoplasm tables (Pycyto_pertime.py:46-49) -------- *
  * cells = skimage.segmentation.expand_labels(nuclei, distance) (0.18.3: nearest label pixel by
  * scipy's exact Euclidean feature transform, kept where the distance <= `distance`);
@@ -577,6 +612,12 @@ int cpx_fov_object_table(cpx_ctx* ctx, const int32_t* labels_dev, int box, int m
  * ascending label order; the CellProfiler step of Feature_extraction_opt.py:164-167).       */
 int cpx_fov_features(cpx_ctx* ctx, const int32_t* labels_dev, int max_objects, double* host_out,
                      int* n_out);
+/* Colocalization rows of every object of labels_dev over the submitted FOV's corrected planes
+ * (cpx_colocalization above): host_out float64 [n][cpx_n_colocalization(C)], row k = k-th object
+ * in ascending label order, the same objects and order as cpx_fov_features.  A FOV submitted
+ * with C == 1 has no columns: only *n_out is set.                                             */
+int cpx_fov_colocalization(cpx_ctx* ctx, const int32_t* labels_dev, int max_objects,
+                           double threshold_pct, double* host_out, int* n_out);
 int cpx_fov_wait(cpx_ctx* ctx);
 
 /* ---- profiling: device time of the k_tex_glcm launches (bench.py's GLCM LDS roofline) ----- *
