@@ -394,8 +394,18 @@ __global__ __launch_bounds__(kTexThreads) void k_intensity_texture(
     const int r0 = o.bbox[0], c0 = o.bbox[1], r1 = o.bbox[2], c1 = o.bbox[3];
     const int bw = c1 - c0;
     const int nb = (r1 - r0) * bw;
+    // the pivot of the variance sums: the first object pixel of bbox row 0 (the bbox is tight), as
+    // k_obj_stage's pivot_col (k_texture.hip int_finish explains the shifted sums)
+    int pc = bw - 1;
+    for (int cc = threadIdx.x; cc < bw; cc += kTexThreads)
+      if (t.lab[(long long)r0 * W + c0 + cc] == t.L) {
+        pc = cc;
+        break;
+      }
+    pc = block_min<int, kTexThreads>(pc, reinterpret_cast<int*>(red));
+    const double pivot = (double)t.img[(long long)r0 * W + c0 + pc];
     // pass 1: object intensity stats + masked-crop min/max (scale_to_8bit range)
-    double s = 0.0, ss = 0.0;
+    double s = 0.0, sd = 0.0, sdd = 0.0;
     float omin = INFINITY, omax = -INFINITY, mmin = INFINITY, mmax = -INFINITY;
     long long n = 0;
     for (int p0 = threadIdx.x; p0 < nb; p0 += 4 * kTexThreads) {
@@ -420,8 +430,10 @@ __global__ __launch_bounds__(kTexThreads) void k_intensity_texture(
         mmax = fmaxf(mmax, m);
         if (ii[u]) {
           n += 1;
+          const double d = (double)v - pivot;
           s += (double)v;
-          ss += (double)v * (double)v;
+          sd += d;
+          sdd = fma(d, d, sdd);
           omin = fminf(omin, v);
           omax = fmaxf(omax, v);
         }
@@ -429,7 +441,8 @@ __global__ __launch_bounds__(kTexThreads) void k_intensity_texture(
     }
     n = block_sum<long long, kTexThreads>(n, red);
     s = block_sum<double, kTexThreads>(s, redd);
-    ss = block_sum<double, kTexThreads>(ss, redd);
+    sd = block_sum<double, kTexThreads>(sd, redd);
+    sdd = block_sum<double, kTexThreads>(sdd, redd);
     omin = block_min<float, kTexThreads>(omin, redf);
     omax = block_max<float, kTexThreads>(omax, redf);
     mmin = block_min<float, kTexThreads>(mmin, redf);
@@ -439,7 +452,7 @@ __global__ __launch_bounds__(kTexThreads) void k_intensity_texture(
                 (long long)ch * CPX_FEATURES_PER_CHANNEL;
     if (threadIdx.x == 0 && ang == 0) {
       const double mean = n ? s / (double)n : 0.0;
-      double var = n ? (ss - s * mean) / (double)n : 0.0;
+      double var = n ? (sdd * (double)n - sd * sd) / ((double)n * (double)n) : 0.0;
       if (var < 0.0) var = 0.0;
       f[CPX_INT_INTEGRATED] = s;
       f[CPX_INT_MEAN] = mean;

@@ -1306,13 +1306,32 @@ __device__ __forceinline__ unsigned int member4(const unsigned int* M, int wpr, 
 __device__ __forceinline__ unsigned int group_desc(const unsigned int* M, int wpr, int bw, int bwp, int W,
                                                    int g) {
   const int f0 = 4 * g, r = f0 / bwp, c = f0 - r * bwp;
-  return (unsigned int)(r * W + c) | (member4(M, wpr, r, c) << 24) | ((unsigned int)min(4, bw - c) << 28);
+  // a group wholly in the row's padding (bw % 8 in 1..4: c >= bw) has no valid pixel: 0, not the
+  // negative bw - c, which read as 15 valid pixels and put the padding's non-members — zeros —
+  // into the scale_to_8bit range of an object that fills its bbox
+  const int nv = max(0, min(4, bw - c));
+  return (unsigned int)(r * W + min(c, bw - 1)) | (member4(M, wpr, r, c) << 24) | ((unsigned int)nv << 28);
 }
 
-// Intensity columns from the member count and sums (regionprops intensity_* in fp64)
-__device__ __noinline__ void int_finish(double* f, long long n, double sm, double ss, float omin, float omax) {
+// bbox column of the first member pixel of bbox row 0 (mask row 2; the bbox is tight, so the row
+// has one): the object's pivot pixel.  Block-uniform, the same for an object on every path.
+__device__ __forceinline__ int pivot_col(const unsigned int* M, int wpr) {
+  const unsigned int* row = M + 2 * wpr;
+  for (int w = 0; w < wpr; ++w)
+    if (row[w]) return w * 32 + __ffs((int)row[w]) - 1 - 2;
+  return 0;
+}
+
+// Intensity columns from the member count and sums (regionprops intensity_* in fp64): sm = sum v
+// (Integrated, Mean); the variance from sd = sum d and sdd = sum d^2 of d = v - pivot, the pivot a
+// pixel of the object (pivot_col).  The single-pass sum v^2 - (sum v)^2 / n cancels to
+// ~n * 2^-53 * mean^2, which is not small beside the variance of a bright, nearly flat object (a
+// constant 40,000-px object at 7e4 read Std 8.8e-4); the shifted sums cancel to ~n * 2^-53 *
+// (mean - pivot)^2, and a constant object gives d = 0, Std exactly 0.
+__device__ __noinline__ void int_finish(double* f, long long n, double sm, double sd, double sdd, float omin,
+                                        float omax) {
   const double mean = n ? sm / (double)n : 0.0;
-  double var = n ? (ss - sm * mean) / (double)n : 0.0;
+  double var = n ? (sdd * (double)n - sd * sd) / ((double)n * (double)n) : 0.0;  // n^2 is exact
   if (var < 0.0) var = 0.0;
   f[CPX_INT_INTEGRATED] = sm;
   f[CPX_INT_MEAN] = mean;
@@ -1341,24 +1360,32 @@ __device__ __forceinline__ void ld_group(float (&dst)[4], const float* img, __am
     dst[3] = t.w;
   } else {
 #pragma unroll
-    for (int u = 0; u < 4; ++u) dst[u] = ldg_b(img, 4u * (o0 + min((unsigned int)u, nv - 1u)));
+    for (int u = 0; u < 4; ++u) dst[u] = ldg_b(img, 4u * (o0 + min((unsigned int)u, max(nv, 1u) - 1u)));
   }
 }
 
+// a block-uniform fp64 value into scalar registers (the pivot stays out of the VGPR budget)
+__device__ __forceinline__ double uniform_f64(double x) {
+  const unsigned long long u = __builtin_bit_cast(unsigned long long, x);
+  const unsigned int lo = __builtin_amdgcn_readfirstlane((unsigned int)u);
+  const unsigned int hi = __builtin_amdgcn_readfirstlane((unsigned int)(u >> 32));
+  return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | lo);
+}
+
 struct IntAcc {
-  long long n;
-  double sm, ss;
-  float omin, omax, mmin, mmax;
+  int n;  // per thread
+  double sm, sd, sdd;  // sum v, sum d, sum d^2 (d = v - pivot, see int_finish)
+  float omin, omax;
+  unsigned int nm;  // non-zero: a valid pixel of the bbox that is no member (a 0 of the masked crop)
 };
 
-__device__ __forceinline__ void int_acc(IntAcc& a, float v, bool in) {
-  const float m = v * (in ? 1.0f : 0.0f);
-  a.mmin = fminf(a.mmin, m);
-  a.mmax = fmaxf(a.mmax, m);
+__device__ __forceinline__ void int_acc(IntAcc& a, float v, bool in, double pivot) {
   if (in) {
+    const double d = (double)v - pivot;
     a.n += 1;
     a.sm += (double)v;
-    a.ss += (double)v * (double)v;
+    a.sd += d;
+    a.sdd = fma(d, d, a.sdd);
     a.omin = fminf(a.omin, v);
     a.omax = fmaxf(a.omax, v);
   }
@@ -1399,9 +1426,9 @@ __global__ __launch_bounds__(kOT) __attribute__((amdgpu_waves_per_eu(stage_wpe(T
   unsigned int* M2 = Bd + kShapeW;  // the twin's membership mask (TWIN only)
   __shared__ long long red[6][kOT / 64];
   __shared__ int redi[3][kOT / 64];
-  __shared__ double sd_[2][2][2][kOT / 64];  // [set / twin][channel parity]: no barrier before the
+  __shared__ double sd_[2][2][3][kOT / 64];  // [set / twin][channel parity]: no barrier before the
   __shared__ long long sn_[2][2][kOT / 64];   // next channel's partials overwrite them
-  __shared__ float sf_[2][2][4][kOT / 64];
+  __shared__ float sf_[2][2][3][kOT / 64];
   __shared__ int s_code;
   const int fov = blockIdx.y, B = gridDim.y;
   const long long N = (long long)H * W;
@@ -1463,8 +1490,12 @@ __global__ __launch_bounds__(kOT) __attribute__((amdgpu_waves_per_eu(stage_wpe(T
     // group descriptors of the register-held groups, the same for every channel: bbox offset of
     // the group's first pixel (< 2^24: shape_fits bounds bh by 4092, and only images with
     // W <= 4096 stage crops)
-    // | member bits << 24 | valid pixels (1..4) << 28
+    // | member bits << 24 | valid pixels (0..4) << 28
     unsigned int gd[kOG], gm2[kOG];  // gm2: the twin's member bits of the same groups
+    // byte offsets of the pivot pixels (int_finish) from the bbox origin, the same for every channel
+    const unsigned int pvo = __builtin_amdgcn_readfirstlane(4u * (unsigned int)pivot_col(M, wpr));
+    const unsigned int pvo2 =
+        TWIN && ky >= 0 ? __builtin_amdgcn_readfirstlane(4u * (unsigned int)pivot_col(M2, wpr)) : pvo;
 #pragma unroll
     for (int i = 0; i < kOG; ++i) {
       const int g = min((int)threadIdx.x + i * kOT, ng - 1);
@@ -1482,8 +1513,10 @@ __global__ __launch_bounds__(kOT) __attribute__((amdgpu_waves_per_eu(stage_wpe(T
       const bool v4 = N < (1LL << 29);  // block-uniform
       const __amdgpu_buffer_rsrc_t rsp =
           __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(plane), (short)0, v4 ? (int)(4 * N) : 0, 0x00020000);
-      IntAcc a{0, 0.0, 0.0, INFINITY, -INFINITY, INFINITY, -INFINITY};
-      IntAcc a2{0, 0.0, 0.0, INFINITY, -INFINITY, INFINITY, -INFINITY};
+      IntAcc a{0, 0.0, 0.0, 0.0, INFINITY, -INFINITY, 0u};
+      IntAcc a2{0, 0.0, 0.0, 0.0, INFINITY, -INFINITY, 0u};
+      const float pvf = ldg_b(img, pvo);
+      const float pvf2 = TWIN && ky >= 0 ? ldg_b(img, pvo2) : pvf;
       float v[kOG][4];
       // opaque per channel: keeps the compiler from hoisting every load's offset out of the
       // channel loop (4 * kOG more VGPRs live across it)
@@ -1494,15 +1527,19 @@ __global__ __launch_bounds__(kOT) __attribute__((amdgpu_waves_per_eu(stage_wpe(T
         const unsigned int o0 = gd[i] & 0xffffffu, nv = gd[i] >> 28;
         ld_group(v[i], img, rsp, img_off, o0, nv, v4);
       }
+      const double pv = uniform_f64((double)pvf);
+      const double pv2 = TWIN && ky >= 0 ? uniform_f64((double)pvf2) : pv;
 #pragma unroll
       for (int i = 0; i < kOG; ++i) {
         if ((int)threadIdx.x + i * kOT >= ng) continue;
         const unsigned int mb = (gd[i] >> 24) & 15u, nv = gd[i] >> 28;
+        a.nm |= ~mb & ((1u << nv) - 1u);
+        if (TWIN && ky >= 0) a2.nm |= ~gm2[i] & ((1u << nv) - 1u);
 #pragma unroll
         for (int u = 0; u < 4; ++u)
           if ((unsigned int)u < nv) {
-            int_acc(a, v[i][u], (mb >> u) & 1u);
-            if (TWIN && ky >= 0) int_acc(a2, v[i][u], (gm2[i] >> u) & 1u);
+            int_acc(a, v[i][u], (mb >> u) & 1u, pv);
+            if (TWIN && ky >= 0) int_acc(a2, v[i][u], (gm2[i] >> u) & 1u, pv2);
           }
       }
       // groups past the register-held ones (large bboxes) are read twice; the block's working
@@ -1525,58 +1562,68 @@ __global__ __launch_bounds__(kOT) __attribute__((amdgpu_waves_per_eu(stage_wpe(T
           if (TWIN && ky >= 0) {
             const int f0 = 4 * (g0 + r * kOT), rr = f0 / bwp, cc = f0 - rr * bwp;
             mb2 = member4(M2, wpr, rr, cc);
+            a2.nm |= ~mb2 & ((1u << nv) - 1u);
           }
+          a.nm |= ~mb & ((1u << nv) - 1u);
 #pragma unroll
           for (int u = 0; u < 4; ++u)
             if ((unsigned int)u < nv) {
-              int_acc(a, w4[r][u], (mb >> u) & 1u);
-              if (TWIN && ky >= 0) int_acc(a2, w4[r][u], (mb2 >> u) & 1u);
+              int_acc(a, w4[r][u], (mb >> u) & 1u, pv);
+              if (TWIN && ky >= 0) int_acc(a2, w4[r][u], (mb2 >> u) & 1u, pv2);
             }
         }
       }
       STAGE_MARK(3, &tprof);
       auto reduce = [&](IntAcc& x, int t, double* fout, float& mmin, float& mmax) {
         // t: which partial slots (0: this set, 1: the twin); channel parity double-buffers them
-        x.n = wave_sum(x.n);
+        const int xn = wave_sum(x.n);  // a wave's members: < 2^31
         x.sm = wave_sum(x.sm);
-        x.ss = wave_sum(x.ss);
+        x.sd = wave_sum(x.sd);
+        x.sdd = wave_sum(x.sdd);
         x.omin = wave_min(x.omin);
         x.omax = wave_max(x.omax);
-        x.mmin = wave_min(x.mmin);
-        x.mmax = wave_max(x.mmax);
+        // the masked crop's range: the members' and, if the bbox holds a non-member, its 0
+        const bool wnm = __builtin_amdgcn_ballot_w64(x.nm != 0u) != 0ull;
         long long* sn = sn_[t][ch & 1];
         double(*sd)[kOT / 64] = sd_[t][ch & 1];
         float(*sf)[kOT / 64] = sf_[t][ch & 1];
         if (lane == 0) {
-          sn[wid] = x.n;
+          sn[wid] = xn;
           sd[0][wid] = x.sm;
-          sd[1][wid] = x.ss;
+          sd[1][wid] = x.sd;
+          sd[2][wid] = x.sdd;
           sf[0][wid] = x.omin;
           sf[1][wid] = x.omax;
-          sf[2][wid] = x.mmin;
-          sf[3][wid] = x.mmax;
+          sf[2][wid] = wnm ? 1.0f : 0.0f;
         }
         __syncthreads();
         // every thread needs only the crop range; thread 0 finishes the Intensity columns
-        mmin = sf[2][0];
-        mmax = sf[3][0];
+        mmin = sf[0][0];
+        mmax = sf[1][0];
+        float anm = sf[2][0];
 #pragma unroll
         for (int w = 1; w < kOT / 64; ++w) {
-          mmin = fminf(mmin, sf[2][w]);
-          mmax = fmaxf(mmax, sf[3][w]);
+          mmin = fminf(mmin, sf[0][w]);
+          mmax = fmaxf(mmax, sf[1][w]);
+          anm = fmaxf(anm, sf[2][w]);
+        }
+        if (anm != 0.0f) {
+          mmin = fminf(mmin, 0.0f);
+          mmax = fmaxf(mmax, 0.0f);
         }
         if (threadIdx.x == 0) {
           long long n = 0;
-          double sm = 0.0, ss = 0.0;
+          double sm = 0.0, sdv = 0.0, sdd = 0.0;
           float omin = INFINITY, omax = -INFINITY;
           for (int w = 0; w < kOT / 64; ++w) {
             n += sn[w];
             sm += sd[0][w];
-            ss += sd[1][w];
+            sdv += sd[1][w];
+            sdd += sd[2][w];
             omin = fminf(omin, sf[0][w]);
             omax = fmaxf(omax, sf[1][w]);
           }
-          int_finish(fout + CPX_N_SHAPE + (long long)ch * CPX_FEATURES_PER_CHANNEL, n, sm, ss, omin, omax);
+          int_finish(fout + CPX_N_SHAPE + (long long)ch * CPX_FEATURES_PER_CHANNEL, n, sm, sdv, sdd, omin, omax);
         }
       };
       float mmin, mmax, mmin2 = 0.0f, mmax2 = 0.0f;

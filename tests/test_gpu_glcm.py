@@ -70,6 +70,9 @@ def test_glcm_paths_match_oracle(dev, kind):
         assert (outl.max(axis=1) > OUT_CAP).all(), outl
     got = _features(dev, lab, planes)
     _feat_close(got, orc.features(lab, planes))
+    # and column class by column class against the exact reference (integer GLCM sums: rtol 1e-9)
+    import features_exact as fx
+    fx.compare(got, *fx.features(lab, planes), what=kind)
 
 
 def test_glcm_mixed_batch_paths_match_oracle(dev):
