@@ -28,6 +28,8 @@ FEATURES_PER_CHANNEL = N_INT + N_TEX
 TEX_DISTANCE = 3
 N_COLOC = 6              # colocalization columns per channel pair
 COLOC_MAX_CHANNELS = 8
+N_IEXT = 14             # intensity-extension columns per channel (CPX_N_IEXT)
+IEXT_LDS_PIXELS = 9216  # largest object cpx_intensity_ext selects from LDS (CPX_IEXT_LDS_PIXELS)
 
 
 class CpxError(RuntimeError):
@@ -108,6 +110,8 @@ SIGNATURES = {
     "cpx_features_pair": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P]),
     "cpx_n_colocalization": (_I, [_I]),
     "cpx_colocalization": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, ct.c_double, _P]),
+    "cpx_n_intensity_ext": (_I, [_I]),
+    "cpx_intensity_ext": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "cpx_csv_format": (_I64, [_I64, _I64, _I, _P, _P, _P, _P, _I64]),
     "cpx_debug_glcm_timing": (_I, [_P, _I]),
     "cpx_debug_glcm_ms": (_I, [_P, ct.POINTER(ct.c_double), ct.POINTER(_I)]),
@@ -141,6 +145,7 @@ SIGNATURES = {
     "cpx_fov_object_table": (_I, [_P, _P, _I, _I, _P, _P]),
     "cpx_fov_features": (_I, [_P, _P, _I, _P, _P]),
     "cpx_fov_colocalization": (_I, [_P, _P, _I, ct.c_double, _P, _P]),
+    "cpx_fov_intensity_ext": (_I, [_P, _P, _I, _P, _P]),
     "cpx_fov_wait": (_I, [_P]),
     "cpx_cpnet_conv3x3": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _I]),
     "cpx_cpnet_conv3x3_head": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P,

@@ -10,6 +10,9 @@ writes those four tables from the GPU pipeline's results:
                  `feature_names(channels)` (AreaShape_*, Intensity_*_<ch>, Texture_*_<ch>_3_<dir>_256)
                  and, with colocalization=True, of `colocalization_names(channels)`
                  (Correlation_{Correlation,Overlap,Manders,K}_<a>_<b> per channel pair)
+                 and, with intensity_ext=True, of `intensity_ext_names(channels)` (quartiles,
+                 median, MAD, edge statistics, mass displacement, Location_CenterMassIntensity_*
+                 and Location_MaxIntensity_* per channel)
 ImageNumber is the 1-based LoadData row; ObjectNumber is the object's label, which the
 segmentation makes consecutive (1..K per image) and which Cells and Cytoplasm share with their
 nucleus.  Rows are sorted by (ImageNumber, ObjectNumber), so the output does not depend on the
@@ -146,6 +149,19 @@ def colocalization_names(channels):
             for n in COLOC_NAMES]
 
 
+# in the order of include/cpx.h CPX_IEXT_*
+IEXT_NAMES = ["Intensity_LowerQuartileIntensity", "Intensity_MedianIntensity", "Intensity_UpperQuartileIntensity",
+              "Intensity_MADIntensity", "Intensity_IntegratedIntensityEdge", "Intensity_MeanIntensityEdge",
+              "Intensity_StdIntensityEdge", "Intensity_MinIntensityEdge", "Intensity_MaxIntensityEdge",
+              "Intensity_MassDisplacement", "Location_CenterMassIntensity_X", "Location_CenterMassIntensity_Y",
+              "Location_MaxIntensity_X", "Location_MaxIntensity_Y"]
+
+
+def intensity_ext_names(channels):
+    """Column names of a cpx_intensity_ext row: 14 columns per channel, channel-major."""
+    return [f"{n}_{ch}" for ch in channels for n in IEXT_NAMES]
+
+
 class _TableStream:
     """Appends formatted CSV blocks to one file on a writer thread, in arrival order, while their
     ImageNumbers increase; finish() reports whether the file is complete and ordered."""
@@ -213,11 +229,13 @@ class PlateTables:
     """Accumulates per-FOV results of one plate/time and writes the four CSVs."""
 
     def __init__(self, channels, eager_csv: bool = False, stream_dir: str | None = None,
-                 colocalization: bool = False):
+                 colocalization: bool = False, intensity_ext: bool = False):
         self.channels = list(channels)
         self.cols = feature_names(self.channels)
         if colocalization:  # rows carry the Correlation_* block after the features (cpx.pipeline)
             self.cols += colocalization_names(self.channels)
+        if intensity_ext:   # ... then the intensity-extension block
+            self.cols += intensity_ext_names(self.channels)
         self.images = []                       # dicts
         self.objects = {t: [] for t in OBJECT_TABLES}  # (ImageNumber, labels[n], feats[n, F])
         # eager_csv: each FOV's object rows are formatted on a thread pool as they are added

@@ -253,6 +253,16 @@ class Device:
                                           _ptr(objects), _ptr(hdr), float(threshold), _ptr(out)),
               "cpx_colocalization")
 
+    def intensity_ext(self, labels, corr, C, max_label, objects, hdr, out):
+        """cpx_intensity_ext: out float64 [B, max_label, n_intensity_ext(C)], row k = the k-th
+        object of the table (rows >= n_objects untouched), 14 columns per channel."""
+        B, H, W = labels.shape
+        assert out.dtype == torch.float64 and out.numel() >= B * max_label * n_intensity_ext(C)
+        self._bind_stream()
+        check(self.lib.cpx_intensity_ext(self.h, _ptr(labels), _ptr(corr), B, C, H, W, max_label,
+                                         _ptr(objects), _ptr(hdr), _ptr(out)),
+              "cpx_intensity_ext")
+
 
 # Pipeline streams with their own CUs (round 5): two pipelines whose streams each hold a CU mask
 # of one contiguous half of the GPU's CUs (hipExtStreamCreateWithCUMask) ran the bench 0.8-0.9 %
@@ -332,6 +342,11 @@ def n_features(C: int) -> int:
 def n_colocalization(C: int) -> int:
     """Columns of a cpx_colocalization row (cpx_n_colocalization): 6 per unordered channel pair."""
     return _lib.N_COLOC * (C * (C - 1) // 2) if C > 0 else 0
+
+
+def n_intensity_ext(C: int) -> int:
+    """Columns of a cpx_intensity_ext row (cpx_n_intensity_ext): 14 per channel."""
+    return _lib.N_IEXT * C if C > 0 else 0
 
 
 def as_numpy(t: torch.Tensor, kind: str):

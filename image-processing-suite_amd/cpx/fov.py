@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check
-from .device import n_colocalization, n_features
+from .device import n_colocalization, n_features, n_intensity_ext
 
 
 class FovSession:
@@ -121,6 +121,19 @@ class FovSession:
         check(self.lib.cpx_fov_colocalization(self.h, ct.c_void_p(lab.data_ptr()), max_objects, float(threshold),
                                               out.ctypes.data_as(ct.c_void_p), ct.byref(n)),
               "cpx_fov_colocalization")
+        return out[: n.value].copy()
+
+    def intensity_ext(self, labels, max_objects: int = 4096) -> np.ndarray:
+        """Intensity-extension rows [n_objects, n_intensity_ext(C)] (quartiles, median, MAD, edge
+        statistics, centre of mass, place of the maximum per channel) of the objects of `labels`
+        over the submitted FOV (the same objects and order as features())."""
+        lab = self._labels(labels)
+        K = n_intensity_ext(self.C)
+        out = np.empty((max_objects, K), np.float64)
+        n = ct.c_int()
+        check(self.lib.cpx_fov_intensity_ext(self.h, ct.c_void_p(lab.data_ptr()), max_objects,
+                                             out.ctypes.data_as(ct.c_void_p), ct.byref(n)),
+              "cpx_fov_intensity_ext")
         return out[: n.value].copy()
 
     def _labels(self, labels):

@@ -26,7 +26,7 @@ import torch
 
 from . import _lib
 from ._lib import COLOC_MAX_CHANNELS
-from .device import Device, as_numpy, n_colocalization, n_features
+from .device import Device, as_numpy, n_colocalization, n_features, n_intensity_ext
 from .segment import CELLPOSE_MODEL, DIAMETER, Segmenter
 
 OBJECT_SETS = ("Nuclei", "Cells", "Cytoplasm")
@@ -75,6 +75,9 @@ class PipelineConfig:
     colocalization: bool = False     # also measure the Correlation_* block (cpx_colocalization):
                                      # FovResults.feats rows get n_colocalization(C) more columns
     coloc_threshold: float = 15.0    # its threshold, percent of the object's channel maximum
+    intensity_ext: bool = False      # also measure the quartile / MAD / edge / location block
+                                     # (cpx_intensity_ext): n_intensity_ext(C) more columns, after
+                                     # the Correlation_* block when both are on
 
     def ws_channel(self) -> int:
         """The watershed elevation channel (cell_channel, or "AGP" / the last channel)."""
@@ -90,7 +93,8 @@ class FovResults:
     hdr: dict                        # set -> structured [B] (n_objects, n_kept, ...)
     objects: dict                    # set -> list of structured arrays (per FOV)
     feats: dict                      # set -> list of float64 [n_objects, F] (F = n_features(C), plus
-                                     # n_colocalization(C) with PipelineConfig.colocalization)
+                                     # n_colocalization(C) with PipelineConfig.colocalization, plus
+                                     # n_intensity_ext(C) with PipelineConfig.intensity_ext)
     seg_stats: np.ndarray
     failed: np.ndarray | None = None  # [B] bool: the FOV's Cells watershed did not converge even
                                       # after the re-runs with more rounds; its object tables are
@@ -154,6 +158,7 @@ class FovPipeline:
         if cfg.colocalization and C > COLOC_MAX_CHANNELS:
             raise ValueError(f"PipelineConfig.colocalization: {C} channels (at most {COLOC_MAX_CHANNELS})")
         self.K = n_colocalization(C) if cfg.colocalization else 0  # appended columns (0: none)
+        self.X = n_intensity_ext(C) if cfg.intensity_ext else 0    # appended after those (0: none)
         self.seg = Segmenter(dev, H, W, B, model=cfg.model, diameter=cfg.diameter, weights=cfg.weights,
                              seed=cfg.seed, use_graph=cfg.use_graph and cfg.cpnet_precision != "fp32",
                              max_objects=ML, resample=cfg.resample, precision=cfg.cpnet_precision)
@@ -171,6 +176,9 @@ class FovPipeline:
             if self.K:
                 self._slots[-1]["coloc"] = {s: torch.zeros((B, ML, self.K), dtype=torch.float64, device=td)
                                             for s in OBJECT_SETS}
+            if self.X:
+                self._slots[-1]["iext"] = {s: torch.zeros((B, ML, self.X), dtype=torch.float64, device=td)
+                                           for s in OBJECT_SETS}
         self._host = {
             "qc": torch.empty(24 * B * C, dtype=torch.uint8, pin_memory=True),
             "hdr": {s: torch.empty(16 * B, dtype=torch.uint8, pin_memory=True) for s in OBJECT_SETS},
@@ -181,6 +189,9 @@ class FovPipeline:
         if self.K:
             self._host["coloc"] = {s: torch.empty(B * ML * self.K, dtype=torch.float64, pin_memory=True)
                                    for s in OBJECT_SETS}
+        if self.X:
+            self._host["iext"] = {s: torch.empty(B * ML * self.X, dtype=torch.float64, pin_memory=True)
+                                  for s in OBJECT_SETS}
         # one result-copy stream per device, shared by its pipelines: a process has only
         # GPU_MAX_HW_QUEUES (4) hardware queues, and streams beyond that share one, which
         # serialises two pipelines' kernels behind each other
@@ -213,6 +224,7 @@ class FovPipeline:
         self.cur = k
         self.qc, self.hdr, self.objects, self.feats = sl["qc"], sl["hdr"], sl["objects"], sl["feats"]
         self.coloc = sl.get("coloc")
+        self.iext = sl.get("iext")
 
     # ---- stages ---------------------------------------------------------------------------
     # A stage in STAGE_EXCLUSIVE (of illum_qc, cpnet, seg_post, cells, features) of one pipeline
@@ -294,6 +306,10 @@ class FovPipeline:
             for s in OBJECT_SETS:
                 self.dev.colocalization(self.labels[s], self.corr, cfg.C, cfg.max_objects, self.objects[s],
                                         self.hdr[s], self.coloc[s], cfg.coloc_threshold)
+        if self.X:
+            for s in OBJECT_SETS:
+                self.dev.intensity_ext(self.labels[s], self.corr, cfg.C, cfg.max_objects, self.objects[s],
+                                       self.hdr[s], self.iext[s])
         if self.cfg.crops:
             self.dev.objects(self.labels["Nuclei"], cfg.max_objects, cfg.box, self.lstats,
                              self.objects["Nuclei"], self.hdr["Nuclei"])
@@ -336,7 +352,7 @@ class FovPipeline:
         from .segment import SEG_ERR_INTERNAL, SEG_OVF_FILL_PARTIAL, SEG_OVF_SEEDS, SEG_STATS_DTYPE
         k = self.cur if slot is None else slot
         sl, hb = self._slots[k], self._host
-        B, ML, F, K = self.cfg.batch, self.cfg.max_objects, self.F, self.K
+        B, ML, F, K, X = self.cfg.batch, self.cfg.max_objects, self.F, self.K, self.X
         cs = self._copy_stream
         cs.wait_event(sl["event"])
         with torch.cuda.stream(cs):
@@ -376,6 +392,10 @@ class FovPipeline:
                     cg = sl["coloc"][s].view(B * ML, K).index_select(0, idx)
                     hb["coloc"][s][:tot * K].view(tot, K).copy_(cg, non_blocking=True)
                     keep.append(cg)
+                if X:
+                    xg = sl["iext"][s].view(B * ML, X).index_select(0, idx)
+                    hb["iext"][s][:tot * X].view(tot, X).copy_(xg, non_blocking=True)
+                    keep.append(xg)
         _sync_after(cs)
         del keep
         objs, feats = {}, {}
@@ -386,6 +406,8 @@ class FovPipeline:
             f = hb["feats"][s][:tot * F].view(tot, F).numpy()
             if K:  # the Correlation_* block follows the features of each row
                 f = np.concatenate([f, hb["coloc"][s][:tot * K].view(tot, K).numpy()], axis=1)
+            if X:  # ... then the intensity-extension block
+                f = np.concatenate([f, hb["iext"][s][:tot * X].view(tot, X).numpy()], axis=1)
             o = as_numpy(hb["objects"][s][:max(tot, 1) * 56], "object")[:tot]
             feats[s] = [f[off[b]:off[b + 1]].copy() for b in range(B)]
             objs[s] = [o[off[b]:off[b + 1]].copy() for b in range(B)]

@@ -102,6 +102,10 @@ def parse_args(argv=None):
     ap.add_argument("--colocalization-threshold", type=float, default=15.0, metavar="PCT",
                     help="threshold of the Overlap / Manders / K columns, percent of the object's maximum "
                          "per channel (default 15)")
+    ap.add_argument("--intensity-extended", action="store_true",
+                    help="also write the per-object intensity quartile, median, MAD, edge, mass-displacement and "
+                         "Location_{CenterMassIntensity,MaxIntensity} columns (PipelineConfig.intensity_ext) after "
+                         "the feature (and Correlation_*) columns")
     return ap.parse_args(argv)
 
 
@@ -271,7 +275,7 @@ def run(argv=None):
         # one rank: each FOV's rows formatted as it finishes and streamed into the job's CSVs
         out = PlateTables(chans, eager_csv=a.world == 1,
                           stream_dir=job_dir(a.out, plate, time) if a.world == 1 else None,
-                          colocalization=a.colocalization)
+                          colocalization=a.colocalization, intensity_ext=a.intensity_extended)
         status = []  # per site: the reference's results_dict entry (Cellpose_GPU_s3fs.py:123-125,219-223)
         d = job_dir(a.out, plate, time)
         try:
@@ -363,7 +367,8 @@ def _run_sites(a, table, source, chans, state, out, status):
         cfg = PipelineConfig(H=H, W=W, C=C, batch=B, channels=tuple(chans), weights=weights,
                              cpnet_precision=getattr(a, "cpnet_precision", "f16x3"),
                              colocalization=bool(getattr(a, "colocalization", False)),
-                             coloc_threshold=float(getattr(a, "colocalization_threshold", 15.0)))
+                             coloc_threshold=float(getattr(a, "colocalization_threshold", 15.0)),
+                             intensity_ext=bool(getattr(a, "intensity_extended", False)))
         if a.ws_rounds:
             cfg.ws_rounds = tuple(a.ws_rounds)
         illum = _illum(a.illum_path, chans, H, W)

@@ -329,6 +329,57 @@ int cpx_colocalization(cpx_ctx* ctx, const int32_t* labels_dev, const float* cor
                        int H, int W, int max_label, const cpx_object* objects_dev,
                        const cpx_fov_objects* hdr_dev, double threshold_pct, double* coloc_dev);
 
+/* ---- a9: per-object intensity quantile, edge and location columns --------------------------- *
+ * The part of CellProfiler 4's MeasureObjectIntensity beyond Integrated / Mean / Std / Min / Max
+ * (restated here, in DESIGN.md §13 and as numpy in tests/intensity_ext_ref.py).  For an object
+ * with label L: P its pixel set, n = |P|; x(p) the fp32 corrected plane of the channel widened
+ * to float64; (r, c) a pixel's integer row and column in the plane; v[0 .. n-1] the x(p) in
+ * ascending order, NaNs last (numpy.sort), -0.0 == +0.0 (a picked zero is written as +0.0).
+ *   q(v, f), f in {1/4, 1/2, 3/4}:  t = n * f, i = floor(t), g = t - i;
+ *                                   v[i] * (1 - g) + v[i+1] * g  if i < n - 1, else v[i]
+ *     (CellProfiler's rule, not numpy.percentile: n = 2 gives the larger value as the median)
+ *   LowerQuartile q(v, 1/4)   Median q(v, 1/2)   UpperQuartile q(v, 3/4)
+ *   MAD           q(w, 1/2), w = |x(p) - Median| over P (one float64 subtraction), ascending
+ *   E = {p in P : p is in the plane's first or last row or column, or one of its 8 neighbours
+ *        has a label != L} (background counts; E is never empty)
+ *   IntegratedIntensityEdge sum_E x      MeanIntensityEdge sum_E x / |E|
+ *   StdIntensityEdge  sqrt(sum_E (x - mean_E)^2 / |E|)   (two-pass, population form)
+ *   Min / MaxIntensityEdge  numpy.min / numpy.max over E (a NaN in E gives NaN)
+ *   CenterMassIntensity_Y  sum_P r x / sum_P x     _X  sum_P c x / sum_P x   (0/0 is NaN)
+ *   MassDisplacement  sqrt((sum_P r / n - CM_Y)^2 + (sum_P c / n - CM_X)^2)
+ *   MaxIntensity_Y, _X  (r, c) of the first pixel in raster order holding the largest value
+ *                       (a NaN counts as the largest, as numpy.argmax has it)
+ * Every float64 sum runs in a fixed order given by the object's bbox and pixel set (no
+ * floating-point atomics): two runs give the same bits.                                       */
+#define CPX_IEXT_LOWER_QUARTILE 0
+#define CPX_IEXT_MEDIAN 1
+#define CPX_IEXT_UPPER_QUARTILE 2
+#define CPX_IEXT_MAD 3
+#define CPX_IEXT_INTEGRATED_EDGE 4
+#define CPX_IEXT_MEAN_EDGE 5
+#define CPX_IEXT_STD_EDGE 6
+#define CPX_IEXT_MIN_EDGE 7
+#define CPX_IEXT_MAX_EDGE 8
+#define CPX_IEXT_MASS_DISPLACEMENT 9
+#define CPX_IEXT_CENTER_MASS_X 10
+#define CPX_IEXT_CENTER_MASS_Y 11
+#define CPX_IEXT_MAX_X 12
+#define CPX_IEXT_MAX_Y 13
+#define CPX_N_IEXT 14
+/* Objects of up to this many pixels are selected from an LDS copy of their values; larger ones
+ * take the same passes over their bbox in global memory (no size limit either way).           */
+#define CPX_IEXT_LDS_PIXELS 9216
+/* Columns of an intensity-extension row: CPX_N_IEXT * C (70 for C = 5, 0 for C < 1).          */
+int cpx_n_intensity_ext(int C);
+/* out_dev: float64 [B][max_label][CPX_N_IEXT * C], channel-major (column CPX_N_IEXT * c + j);
+ * row k is the k-th object of the FOV's table (objects_dev / hdr_dev as cpx_objects wrote them
+ * for labels_dev; rows >= n_objects untouched).  A table row is trusted for its label only: the
+ * bbox is cut to the plane.  Any C >= 1 (C < 1 is CPX_ERR_ARG); H * W < 2^31.  Runs on the
+ * context's current stream.                                                                    */
+int cpx_intensity_ext(cpx_ctx* ctx, const int32_t* labels_dev, const float* corr_dev, int B, int C,
+                      int H, int W, int max_label, const cpx_object* objects_dev,
+                      const cpx_fov_objects* hdr_dev, double* out_dev);
+
 /* ---- secondary objects for the Cells / Cytoplasm tables (Pycyto_pertime.py:46-49) -------- *
  * cells = skimage.segmentation.expand_labels(nuclei, distance) (0.18.3: nearest label pixel by
  * scipy's exact Euclidean feature transform, kept where the distance <= `distance`);
@@ -618,6 +669,11 @@ int cpx_fov_features(cpx_ctx* ctx, const int32_t* labels_dev, int max_objects, d
  * with C == 1 has no columns: only *n_out is set.                                             */
 int cpx_fov_colocalization(cpx_ctx* ctx, const int32_t* labels_dev, int max_objects,
                            double threshold_pct, double* host_out, int* n_out);
+/* Intensity-extension rows (cpx_intensity_ext above) of every object of labels_dev over the
+ * submitted FOV's corrected planes: host_out float64 [n][cpx_n_intensity_ext(C)], the same
+ * objects and order as cpx_fov_features.                                                      */
+int cpx_fov_intensity_ext(cpx_ctx* ctx, const int32_t* labels_dev, int max_objects, double* host_out,
+                          int* n_out);
 int cpx_fov_wait(cpx_ctx* ctx);
 
 /* ---- profiling: device time of the k_tex_glcm launches (bench.py's GLCM LDS roofline) ----- *
