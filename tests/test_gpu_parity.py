@@ -94,16 +94,21 @@ def test_illum_qc_full_fov_batched(dev, golden_dir):
 
 def test_qc_rows_2080_matches_generic_fft(dev, monkeypatch):
     """The W = 2080 row pass (k_qc_rows_2080: three register passes, pruned last pass) against the
-    generic Stockham row pass on the same planes — ordinary FOVs, an odd row count (H = 2079: the
-    last row pair has one row), a constant plane, a NaN pixel, a plane that is mostly its mean."""
+    generic Stockham row pass on the same planes — ordinary FOVs, an odd row count (H = 2197: the
+    last row pair has one row and the last block 3 of its 4 row pairs; the fast kernel needs
+    W == 2080 and min(H, W) // 8 == 260, so a shorter odd H such as 2079 would run the generic
+    kernel twice), a constant plane, a NaN pixel, a plane that is mostly its mean.  Against
+    numpy: tests/test_gpu_qc_shapes.py."""
     rng = np.random.default_rng(31)
-    H, W = 2080, 2080
-    raw = rng.integers(100, 4000, (5, H, W), dtype=np.uint16)
-    raw[1] = 1234
-    raw[3, :1500] = 777
-    ill = (0.7 + 0.6 * rng.random((1, H, W))).astype(np.float32)
+    H, W, H_odd = 2080, 2080, 2197
+    assert min(H_odd, W) // 8 == 260 and H_odd % 2 == 1 and ((H_odd + 1) // 2) % 4 == 3
+    raw_odd = rng.integers(100, 4000, (5, H_odd, W), dtype=np.uint16)
+    raw_odd[1] = 1234
+    raw_odd[3, :1500] = 777
+    ill_odd = (0.7 + 0.6 * rng.random((1, H_odd, W))).astype(np.float32)
+    raw, ill = np.ascontiguousarray(raw_odd[:, :H]), np.ascontiguousarray(ill_odd[:, :H])
     ill_nan = ill.copy()
-    for case_raw, case_ill, h in ((raw, ill, H), (raw[:, :2079], ill[:, :2079], 2079), (raw[4:5], ill_nan, H)):
+    for case_raw, case_ill, h in ((raw, ill, H), (raw_odd, ill_odd, H_odd), (raw[4:5], ill_nan, H)):
         if case_ill is ill_nan:
             case_ill = case_ill.copy()
             case_ill[0, 17, 33] = np.nan
