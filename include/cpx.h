@@ -398,7 +398,9 @@ int cpx_expand_labels(cpx_ctx* ctx, const int32_t* nuclei_dev, int B, int H, int
  * `label_rounds` pointer-jumping rounds, without host synchronisation; status_dev[b *
  * status_stride] (int32) receives 100 * (relax rounds used) + (jump rounds used), or -1 when the
  * rounds enqueued did not reach the fixed point (labels then invalid; the host must raise).
- * H * W <= 2^23.                                                                               */
+ * H * W <= 2^23, distance 0..127, both round counts 1..64.  Nuclei label values must be below
+ * 2^23: the footprint comes from the packed expand pass (label << 8 | row offset), which a
+ * larger label overflows (2^24 packs to 0: its surroundings would fall out of the mask).        */
 int cpx_watershed_cells(cpx_ctx* ctx, const int32_t* nuclei_dev, const float* corr_dev, int B, int C,
                         int cell_channel, int H, int W, int distance, int relax_rounds,
                         int label_rounds, int32_t* cells_dev, int32_t* cyto_dev, int32_t* status_dev,
