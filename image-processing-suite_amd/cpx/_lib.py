@@ -30,6 +30,7 @@ N_COLOC = 6              # colocalization columns per channel pair
 COLOC_MAX_CHANNELS = 8
 N_IEXT = 14             # intensity-extension columns per channel (CPX_N_IEXT)
 IEXT_LDS_PIXELS = 9216  # largest object cpx_intensity_ext selects from LDS (CPX_IEXT_LDS_PIXELS)
+N_HAR = 9               # Haralick columns per channel and direction (CPX_N_HAR)
 
 
 class CpxError(RuntimeError):
@@ -112,6 +113,8 @@ SIGNATURES = {
     "cpx_colocalization": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, ct.c_double, _P]),
     "cpx_n_intensity_ext": (_I, [_I]),
     "cpx_intensity_ext": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "cpx_n_texture_haralick": (_I, [_I]),
+    "cpx_texture_haralick": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "cpx_csv_format": (_I64, [_I64, _I64, _I, _P, _P, _P, _P, _I64]),
     "cpx_debug_glcm_timing": (_I, [_P, _I]),
     "cpx_debug_glcm_ms": (_I, [_P, ct.POINTER(ct.c_double), ct.POINTER(_I)]),
@@ -146,6 +149,7 @@ SIGNATURES = {
     "cpx_fov_features": (_I, [_P, _P, _I, _P, _P]),
     "cpx_fov_colocalization": (_I, [_P, _P, _I, ct.c_double, _P, _P]),
     "cpx_fov_intensity_ext": (_I, [_P, _P, _I, _P, _P]),
+    "cpx_fov_texture_haralick": (_I, [_P, _P, _I, _P, _P]),
     "cpx_fov_wait": (_I, [_P]),
     "cpx_cpnet_conv3x3": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _I]),
     "cpx_cpnet_conv3x3_head": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P,

@@ -13,6 +13,8 @@ writes those four tables from the GPU pipeline's results:
                  and, with intensity_ext=True, of `intensity_ext_names(channels)` (quartiles,
                  median, MAD, edge statistics, mass displacement, Location_CenterMassIntensity_*
                  and Location_MaxIntensity_* per channel)
+                 and, with texture_haralick=True, of `haralick_names(channels)` (the nine Haralick
+                 Texture_* columns the feature block lacks, per channel and direction)
 ImageNumber is the 1-based LoadData row; ObjectNumber is the object's label, which the
 segmentation makes consecutive (1..K per image) and which Cells and Cytoplasm share with their
 nucleus.  Rows are sorted by (ImageNumber, ObjectNumber), so the output does not depend on the
@@ -162,6 +164,18 @@ def intensity_ext_names(channels):
     return [f"{n}_{ch}" for ch in channels for n in IEXT_NAMES]
 
 
+# in the order of include/cpx.h CPX_HAR_*
+HARALICK_NAMES = ["Variance", "SumAverage", "SumVariance", "SumEntropy", "Entropy", "DifferenceVariance",
+                  "DifferenceEntropy", "InfoMeas1", "InfoMeas2"]
+
+
+def haralick_names(channels):
+    """Column names of a cpx_texture_haralick row: Texture_<F>_<ch>_3_<dd>_256, nine per channel and
+    direction, channel-major, then direction (the scheme of the Texture_* names of feature_names)."""
+    return [f"Texture_{n}_{ch}_{TEXTURE_SCALE}_{d:02d}_256" for ch in channels for d in range(4)
+            for n in HARALICK_NAMES]
+
+
 class _TableStream:
     """Appends formatted CSV blocks to one file on a writer thread, in arrival order, while their
     ImageNumbers increase; finish() reports whether the file is complete and ordered."""
@@ -229,13 +243,15 @@ class PlateTables:
     """Accumulates per-FOV results of one plate/time and writes the four CSVs."""
 
     def __init__(self, channels, eager_csv: bool = False, stream_dir: str | None = None,
-                 colocalization: bool = False, intensity_ext: bool = False):
+                 colocalization: bool = False, intensity_ext: bool = False, texture_haralick: bool = False):
         self.channels = list(channels)
         self.cols = feature_names(self.channels)
         if colocalization:  # rows carry the Correlation_* block after the features (cpx.pipeline)
             self.cols += colocalization_names(self.channels)
         if intensity_ext:   # ... then the intensity-extension block
             self.cols += intensity_ext_names(self.channels)
+        if texture_haralick:  # ... then the Haralick texture block
+            self.cols += haralick_names(self.channels)
         self.images = []                       # dicts
         self.objects = {t: [] for t in OBJECT_TABLES}  # (ImageNumber, labels[n], feats[n, F])
         # eager_csv: each FOV's object rows are formatted on a thread pool as they are added

@@ -263,6 +263,16 @@ class Device:
                                          _ptr(objects), _ptr(hdr), _ptr(out)),
               "cpx_intensity_ext")
 
+    def texture_haralick(self, labels, corr, C, max_label, objects, hdr, out):
+        """cpx_texture_haralick: out float64 [B, max_label, n_texture_haralick(C)], row k = the k-th
+        object of the table (rows >= n_objects untouched), column (c * 4 + d) * 9 + j."""
+        B, H, W = labels.shape
+        assert out.dtype == torch.float64 and out.numel() >= B * max_label * n_texture_haralick(C)
+        self._bind_stream()
+        check(self.lib.cpx_texture_haralick(self.h, _ptr(labels), _ptr(corr), B, C, H, W, max_label,
+                                            _ptr(objects), _ptr(hdr), _ptr(out)),
+              "cpx_texture_haralick")
+
 
 # Pipeline streams with their own CUs (round 5): two pipelines whose streams each hold a CU mask
 # of one contiguous half of the GPU's CUs (hipExtStreamCreateWithCUMask) ran the bench 0.8-0.9 %
@@ -347,6 +357,11 @@ def n_colocalization(C: int) -> int:
 def n_intensity_ext(C: int) -> int:
     """Columns of a cpx_intensity_ext row (cpx_n_intensity_ext): 14 per channel."""
     return _lib.N_IEXT * C if C > 0 else 0
+
+
+def n_texture_haralick(C: int) -> int:
+    """Columns of a cpx_texture_haralick row (cpx_n_texture_haralick): 9 per channel and direction."""
+    return 4 * _lib.N_HAR * C if C > 0 else 0
 
 
 def as_numpy(t: torch.Tensor, kind: str):

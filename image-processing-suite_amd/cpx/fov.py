@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import check
-from .device import n_colocalization, n_features, n_intensity_ext
+from .device import n_colocalization, n_features, n_intensity_ext, n_texture_haralick
 
 
 class FovSession:
@@ -134,6 +134,19 @@ class FovSession:
         check(self.lib.cpx_fov_intensity_ext(self.h, ct.c_void_p(lab.data_ptr()), max_objects,
                                              out.ctypes.data_as(ct.c_void_p), ct.byref(n)),
               "cpx_fov_intensity_ext")
+        return out[: n.value].copy()
+
+    def texture_haralick(self, labels, max_objects: int = 4096) -> np.ndarray:
+        """Haralick texture rows [n_objects, n_texture_haralick(C)] (Variance, Sum*, Entropy,
+        Difference*, InfoMeas1/2 per channel and direction) of the objects of `labels` over the
+        submitted FOV (the same objects and order as features())."""
+        lab = self._labels(labels)
+        K = n_texture_haralick(self.C)
+        out = np.empty((max_objects, K), np.float64)
+        n = ct.c_int()
+        check(self.lib.cpx_fov_texture_haralick(self.h, ct.c_void_p(lab.data_ptr()), max_objects,
+                                                out.ctypes.data_as(ct.c_void_p), ct.byref(n)),
+              "cpx_fov_texture_haralick")
         return out[: n.value].copy()
 
     def _labels(self, labels):

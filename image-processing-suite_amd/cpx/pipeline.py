@@ -26,7 +26,7 @@ import torch
 
 from . import _lib
 from ._lib import COLOC_MAX_CHANNELS
-from .device import Device, as_numpy, n_colocalization, n_features, n_intensity_ext
+from .device import Device, as_numpy, n_colocalization, n_features, n_intensity_ext, n_texture_haralick
 from .segment import CELLPOSE_MODEL, DIAMETER, Segmenter
 
 OBJECT_SETS = ("Nuclei", "Cells", "Cytoplasm")
@@ -78,6 +78,9 @@ class PipelineConfig:
     intensity_ext: bool = False      # also measure the quartile / MAD / edge / location block
                                      # (cpx_intensity_ext): n_intensity_ext(C) more columns, after
                                      # the Correlation_* block when both are on
+    texture_haralick: bool = False   # also measure the nine Haralick columns the Texture_* block
+                                     # lacks (cpx_texture_haralick): n_texture_haralick(C) more
+                                     # columns, after the blocks above
 
     def ws_channel(self) -> int:
         """The watershed elevation channel (cell_channel, or "AGP" / the last channel)."""
@@ -94,7 +97,8 @@ class FovResults:
     objects: dict                    # set -> list of structured arrays (per FOV)
     feats: dict                      # set -> list of float64 [n_objects, F] (F = n_features(C), plus
                                      # n_colocalization(C) with PipelineConfig.colocalization, plus
-                                     # n_intensity_ext(C) with PipelineConfig.intensity_ext)
+                                     # n_intensity_ext(C) with PipelineConfig.intensity_ext, plus
+                                     # n_texture_haralick(C) with PipelineConfig.texture_haralick)
     seg_stats: np.ndarray
     failed: np.ndarray | None = None  # [B] bool: the FOV's Cells watershed did not converge even
                                       # after the re-runs with more rounds; its object tables are
@@ -159,6 +163,7 @@ class FovPipeline:
             raise ValueError(f"PipelineConfig.colocalization: {C} channels (at most {COLOC_MAX_CHANNELS})")
         self.K = n_colocalization(C) if cfg.colocalization else 0  # appended columns (0: none)
         self.X = n_intensity_ext(C) if cfg.intensity_ext else 0    # appended after those (0: none)
+        self.T = n_texture_haralick(C) if cfg.texture_haralick else 0  # ... and after those
         self.seg = Segmenter(dev, H, W, B, model=cfg.model, diameter=cfg.diameter, weights=cfg.weights,
                              seed=cfg.seed, use_graph=cfg.use_graph and cfg.cpnet_precision != "fp32",
                              max_objects=ML, resample=cfg.resample, precision=cfg.cpnet_precision)
@@ -179,6 +184,9 @@ class FovPipeline:
             if self.X:
                 self._slots[-1]["iext"] = {s: torch.zeros((B, ML, self.X), dtype=torch.float64, device=td)
                                            for s in OBJECT_SETS}
+            if self.T:
+                self._slots[-1]["har"] = {s: torch.zeros((B, ML, self.T), dtype=torch.float64, device=td)
+                                          for s in OBJECT_SETS}
         self._host = {
             "qc": torch.empty(24 * B * C, dtype=torch.uint8, pin_memory=True),
             "hdr": {s: torch.empty(16 * B, dtype=torch.uint8, pin_memory=True) for s in OBJECT_SETS},
@@ -192,6 +200,9 @@ class FovPipeline:
         if self.X:
             self._host["iext"] = {s: torch.empty(B * ML * self.X, dtype=torch.float64, pin_memory=True)
                                   for s in OBJECT_SETS}
+        if self.T:
+            self._host["har"] = {s: torch.empty(B * ML * self.T, dtype=torch.float64, pin_memory=True)
+                                 for s in OBJECT_SETS}
         # one result-copy stream per device, shared by its pipelines: a process has only
         # GPU_MAX_HW_QUEUES (4) hardware queues, and streams beyond that share one, which
         # serialises two pipelines' kernels behind each other
@@ -225,6 +236,7 @@ class FovPipeline:
         self.qc, self.hdr, self.objects, self.feats = sl["qc"], sl["hdr"], sl["objects"], sl["feats"]
         self.coloc = sl.get("coloc")
         self.iext = sl.get("iext")
+        self.har = sl.get("har")
 
     # ---- stages ---------------------------------------------------------------------------
     # A stage in STAGE_EXCLUSIVE (of illum_qc, cpnet, seg_post, cells, features) of one pipeline
@@ -310,6 +322,10 @@ class FovPipeline:
             for s in OBJECT_SETS:
                 self.dev.intensity_ext(self.labels[s], self.corr, cfg.C, cfg.max_objects, self.objects[s],
                                        self.hdr[s], self.iext[s])
+        if self.T:
+            for s in OBJECT_SETS:
+                self.dev.texture_haralick(self.labels[s], self.corr, cfg.C, cfg.max_objects, self.objects[s],
+                                          self.hdr[s], self.har[s])
         if self.cfg.crops:
             self.dev.objects(self.labels["Nuclei"], cfg.max_objects, cfg.box, self.lstats,
                              self.objects["Nuclei"], self.hdr["Nuclei"])
@@ -352,7 +368,7 @@ class FovPipeline:
         from .segment import SEG_ERR_INTERNAL, SEG_OVF_FILL_PARTIAL, SEG_OVF_SEEDS, SEG_STATS_DTYPE
         k = self.cur if slot is None else slot
         sl, hb = self._slots[k], self._host
-        B, ML, F, K, X = self.cfg.batch, self.cfg.max_objects, self.F, self.K, self.X
+        B, ML, F, K, X, T = self.cfg.batch, self.cfg.max_objects, self.F, self.K, self.X, self.T
         cs = self._copy_stream
         cs.wait_event(sl["event"])
         with torch.cuda.stream(cs):
@@ -396,6 +412,10 @@ class FovPipeline:
                     xg = sl["iext"][s].view(B * ML, X).index_select(0, idx)
                     hb["iext"][s][:tot * X].view(tot, X).copy_(xg, non_blocking=True)
                     keep.append(xg)
+                if T:
+                    tg = sl["har"][s].view(B * ML, T).index_select(0, idx)
+                    hb["har"][s][:tot * T].view(tot, T).copy_(tg, non_blocking=True)
+                    keep.append(tg)
         _sync_after(cs)
         del keep
         objs, feats = {}, {}
@@ -408,6 +428,8 @@ class FovPipeline:
                 f = np.concatenate([f, hb["coloc"][s][:tot * K].view(tot, K).numpy()], axis=1)
             if X:  # ... then the intensity-extension block
                 f = np.concatenate([f, hb["iext"][s][:tot * X].view(tot, X).numpy()], axis=1)
+            if T:  # ... then the Haralick texture block
+                f = np.concatenate([f, hb["har"][s][:tot * T].view(tot, T).numpy()], axis=1)
             o = as_numpy(hb["objects"][s][:max(tot, 1) * 56], "object")[:tot]
             feats[s] = [f[off[b]:off[b + 1]].copy() for b in range(B)]
             objs[s] = [o[off[b]:off[b + 1]].copy() for b in range(B)]

@@ -106,6 +106,11 @@ def parse_args(argv=None):
                     help="also write the per-object intensity quartile, median, MAD, edge, mass-displacement and "
                          "Location_{CenterMassIntensity,MaxIntensity} columns (PipelineConfig.intensity_ext) after "
                          "the feature (and Correlation_*) columns")
+    ap.add_argument("--texture-haralick", action="store_true",
+                    help="also write the nine Haralick Texture_* columns the feature block lacks (Variance, "
+                         "SumAverage, SumVariance, SumEntropy, Entropy, DifferenceVariance, DifferenceEntropy, "
+                         "InfoMeas1, InfoMeas2 per channel and direction; PipelineConfig.texture_haralick) after "
+                         "the columns above")
     return ap.parse_args(argv)
 
 
@@ -275,7 +280,8 @@ def run(argv=None):
         # one rank: each FOV's rows formatted as it finishes and streamed into the job's CSVs
         out = PlateTables(chans, eager_csv=a.world == 1,
                           stream_dir=job_dir(a.out, plate, time) if a.world == 1 else None,
-                          colocalization=a.colocalization, intensity_ext=a.intensity_extended)
+                          colocalization=a.colocalization, intensity_ext=a.intensity_extended,
+                          texture_haralick=a.texture_haralick)
         status = []  # per site: the reference's results_dict entry (Cellpose_GPU_s3fs.py:123-125,219-223)
         d = job_dir(a.out, plate, time)
         try:
@@ -368,7 +374,8 @@ def _run_sites(a, table, source, chans, state, out, status):
                              cpnet_precision=getattr(a, "cpnet_precision", "f16x3"),
                              colocalization=bool(getattr(a, "colocalization", False)),
                              coloc_threshold=float(getattr(a, "colocalization_threshold", 15.0)),
-                             intensity_ext=bool(getattr(a, "intensity_extended", False)))
+                             intensity_ext=bool(getattr(a, "intensity_extended", False)),
+                             texture_haralick=bool(getattr(a, "texture_haralick", False)))
         if a.ws_rounds:
             cfg.ws_rounds = tuple(a.ws_rounds)
         illum = _illum(a.illum_path, chans, H, W)

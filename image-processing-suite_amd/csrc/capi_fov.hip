@@ -38,6 +38,8 @@ struct cpx_fov_state {
   size_t coloc_cap = 0;
   double* iext = nullptr;     // [max_objects][cpx_n_intensity_ext(C)] (cpx_fov_intensity_ext)
   size_t iext_cap = 0;
+  double* har = nullptr;      // [max_objects][cpx_n_texture_haralick(C)] (cpx_fov_texture_haralick)
+  size_t har_cap = 0;
 };
 
 void cpx_fov_free(cpx_ctx* ctx) {
@@ -46,7 +48,7 @@ void cpx_fov_free(cpx_ctx* ctx) {
   for (void* p : f->illum)
     if (p) (void)hipFree(p);
   void* bufs[] = {f->raw, f->zplane, f->corr, f->stats, f->qc,
-                  f->lstats, f->objects, f->hdr, f->feats, f->yf, f->coloc, f->iext};
+                  f->lstats, f->objects, f->hdr, f->feats, f->yf, f->coloc, f->iext, f->har};
   for (void* p : bufs)
     if (p) (void)hipFree(p);
   delete f;
@@ -338,6 +340,29 @@ int cpx_fov_intensity_ext(cpx_ctx* ctx, const int32_t* labels_dev, int max_objec
     return rc;
   if (host_out && *n_out > 0) {
     CPX_CHECK_HIP(hipMemcpyAsync(host_out, f->iext, sizeof(double) * K * (*n_out), hipMemcpyDeviceToHost,
+                                 ctx->stream));
+  }
+  CPX_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  return CPX_OK;
+}
+
+int cpx_fov_texture_haralick(cpx_ctx* ctx, const int32_t* labels_dev, int max_objects, double* host_out,
+                             int* n_out) {
+  CPX_REQUIRE(ctx && labels_dev && n_out && max_objects > 0, CPX_ERR_ARG,
+              "cpx_fov_texture_haralick: bad argument");
+  CPX_REQUIRE(ctx->fov && ctx->fov->have, CPX_ERR_STATE, "cpx_fov_texture_haralick: no FOV submitted");
+  cpx_fov_state* f = ctx->fov;
+  int rc;
+  if ((rc = cpx_fov_object_table(ctx, labels_dev, 0, max_objects, nullptr, n_out)) != CPX_OK) return rc;
+  const size_t K = (size_t)cpx_n_texture_haralick(f->C);
+  if ((rc = grow(ctx, (void**)&f->har, &f->har_cap, sizeof(double) * K * max_objects,
+                 "fov Haralick texture")) != CPX_OK)
+    return rc;
+  if ((rc = cpx_texture_haralick(ctx, labels_dev, f->corr, 1, f->C, f->H, f->W, max_objects, f->objects,
+                                 f->hdr, f->har)) != CPX_OK)
+    return rc;
+  if (host_out && *n_out > 0) {
+    CPX_CHECK_HIP(hipMemcpyAsync(host_out, f->har, sizeof(double) * K * (*n_out), hipMemcpyDeviceToHost,
                                  ctx->stream));
   }
   CPX_CHECK_HIP(hipStreamSynchronize(ctx->stream));

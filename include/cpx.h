@@ -380,6 +380,55 @@ int cpx_intensity_ext(cpx_ctx* ctx, const int32_t* labels_dev, const float* corr
                       int H, int W, int max_label, const cpx_object* objects_dev,
                       const cpx_fov_objects* hdr_dev, double* out_dev);
 
+/* ---- a9: the Haralick texture columns the Texture_* block lacks ----------------------------- *
+ * Nine of Haralick's 13 features per object, channel and direction (restated here, in DESIGN.md
+ * §14 and as numpy in tests/haralick_ref.py); the other four are the existing columns Contrast,
+ * AngularSecondMoment, Correlation and Homogeneity (= InverseDifferenceMoment).  For an object
+ * with label L, a channel and a direction d in 0..3, N is the count matrix the existing
+ * Texture_* columns are computed from: 256 levels, not symmetric, N(i, j) = the number of pixel
+ * pairs (p, p + offset_d) inside the object's bbox with level i at p (the reference pixel) and j
+ * at p + offset_d; offsets (row, column) = (0, 3), (2, 2), (3, 0), (2, -2); the levels are
+ * scale_to_8bit of the masked bbox crop (the plane's values times (label == L), so pixels of the
+ * bbox outside the object count as 0 and pairs with them are included).
+ *   T = sum N, P = N / T;  px(i) = sum_j P(i, j), py(j) = sum_i P(i, j),
+ *   psum(k) = sum_{i + j = k} P (k = 0..510), pdiff(k) = sum_{|i - j| = k} P (k = 0..255),
+ *   H(q) = -sum_{q > 0} q log2 q  (+0.0 for a vector with one occupied bin)
+ *   Variance            sum_i (i - mu_x)^2 px(i), mu_x = sum_i i px(i)
+ *   SumAverage          sum_k k psum(k)
+ *   SumVariance         sum_k (k - SumAverage)^2 psum(k)
+ *   SumEntropy          H(psum)
+ *   Entropy             HXY = H(P)
+ *   DifferenceVariance  sum_k (k - mu_d)^2 pdiff(k), mu_d = sum_k k pdiff(k)   (Haralick's form;
+ *                       mahotas / CellProfiler take numpy.var of the 256 entries of pdiff)
+ *   DifferenceEntropy   H(pdiff)
+ *   InfoMeas1           (HXY - HX - HY) / max(HX, HY), HX = H(px), HY = H(py); 0.0 if the max is 0
+ *   InfoMeas2           sqrt(max(0, 1 - exp(-2 (HX + HY - HXY))))  (entropies in bits, exp natural;
+ *                       Haralick's HXY1 and HXY2 both equal HX + HY exactly)
+ * T = 0 (the bbox is narrower or shorter than the offset) gives nine +0.0.  Every column is
+ * finite when the pixels are finite and 255 * (max - min) of the crop is finite in fp32; on
+ * other input the levels are whatever the shared quantiser makes of it.  Every float64 sum runs
+ * in a fixed order (integer LDS atomics only): two runs give the same bits.                   */
+#define CPX_HAR_VARIANCE 0
+#define CPX_HAR_SUM_AVERAGE 1
+#define CPX_HAR_SUM_VARIANCE 2
+#define CPX_HAR_SUM_ENTROPY 3
+#define CPX_HAR_ENTROPY 4
+#define CPX_HAR_DIFFERENCE_VARIANCE 5
+#define CPX_HAR_DIFFERENCE_ENTROPY 6
+#define CPX_HAR_INFO_MEAS1 7
+#define CPX_HAR_INFO_MEAS2 8
+#define CPX_N_HAR 9
+/* Columns of a Haralick row: 4 * CPX_N_HAR * C (180 for C = 5, 0 for C < 1).                  */
+int cpx_n_texture_haralick(int C);
+/* out_dev: float64 [B][max_label][C][4][CPX_N_HAR] (column (c * 4 + d) * CPX_N_HAR + j); row k is
+ * the k-th object of the FOV's table (objects_dev / hdr_dev as cpx_objects wrote them for
+ * labels_dev; rows >= n_objects untouched).  A table row is trusted for its label only: the bbox
+ * is cut to the plane.  Any object size, any C >= 1 (C < 1 is CPX_ERR_ARG); H * W < 2^31; no
+ * workspace.  Runs on the context's current stream.                                           */
+int cpx_texture_haralick(cpx_ctx* ctx, const int32_t* labels_dev, const float* corr_dev, int B, int C,
+                         int H, int W, int max_label, const cpx_object* objects_dev,
+                         const cpx_fov_objects* hdr_dev, double* out_dev);
+
 /* ---- secondary objects for the Cells / Cytoplasm tables (Pycyto_pertime.py:46-49) -------- *
  * cells = skimage.segmentation.expand_labels(nuclei, distance) (0.18.3: nearest label pixel by
  * scipy's exact Euclidean feature transform, kept where the distance <= `distance`);
@@ -676,6 +725,11 @@ int cpx_fov_colocalization(cpx_ctx* ctx, const int32_t* labels_dev, int max_obje
  * objects and order as cpx_fov_features.                                                      */
 int cpx_fov_intensity_ext(cpx_ctx* ctx, const int32_t* labels_dev, int max_objects, double* host_out,
                           int* n_out);
+/* Haralick texture rows (cpx_texture_haralick above) of every object of labels_dev over the
+ * submitted FOV's corrected planes: host_out float64 [n][cpx_n_texture_haralick(C)], the same
+ * objects and order as cpx_fov_features.                                                      */
+int cpx_fov_texture_haralick(cpx_ctx* ctx, const int32_t* labels_dev, int max_objects, double* host_out,
+                             int* n_out);
 int cpx_fov_wait(cpx_ctx* ctx);
 
 /* ---- profiling: device time of the k_tex_glcm launches (bench.py's GLCM LDS roofline) ----- *
