@@ -239,13 +239,21 @@ __global__ __launch_bounds__(kST) void k_robust_mad(const double* __restrict__ m
   int n2;
   const int m = gather_sorted(mat + (long long)j * N, fit, n_fit, a, &cnt, &n2);
   const double md = median_sorted(a, m);
+  // scipy takes np.median of |x - med|.  An infinite median that some value equals leaves
+  // inf - inf = NaN among the deviations (a NaN median, from a middle pair (-inf, +inf), NaN
+  // everywhere), and np.median of an array that holds NaN is NaN.  Read off the sorted
+  // extremes (block-uniform): a comparison network cannot order NaN, so none is ever sorted.
+  const bool nan_dev =
+      m > 0 && (md != md || (isinf(md) && (md > 0.0 ? a[m - 1] == md : a[0] == md)));
   __syncthreads();
-  for (int i = threadIdx.x; i < n2; i += kST) a[i] = i < m ? fabs(a[i] - md) : __builtin_inf();
-  __syncthreads();
-  block_sort(a, n2);
+  if (!nan_dev) {
+    for (int i = threadIdx.x; i < n2; i += kST) a[i] = i < m ? fabs(a[i] - md) : __builtin_inf();
+    __syncthreads();
+    block_sort(a, n2);
+  }
   if (threadIdx.x == 0) {
     med[j] = md;
-    mad[j] = m ? median_sorted(a, m) / scale : __builtin_nan("");
+    mad[j] = m && !nan_dev ? median_sorted(a, m) / scale : __builtin_nan("");
   }
 }
 
@@ -399,6 +407,9 @@ extern "C" int cpx_group_median(cpx_ctx* ctx, const double* values_dev, int n_ro
               CPX_ERR_ARG, "cpx_group_median: bad argument (at most 16384 rows per group)");
   int n2 = 1;
   while (n2 < max_group_rows) n2 <<= 1;
+  // up to 128 KB of dynamic LDS (groups past 8192 rows).  The HIP runtime launches this on
+  // gfx950 (160 KB per workgroup) without hipFuncAttributeMaxDynamicSharedMemorySize being
+  // raised first: tests/test_gpu_profiles_edges.py runs groups of 8193 and 16384 rows.
   hipLaunchKernelGGL(k_group_median, dim3(K, G), dim3(kST), sizeof(double) * n2, ctx->stream,
                      values_dev, K, ld, (const int*)order_dev, (const int*)offs_dev, row_scale_dev,
                      (const unsigned char*)col_scaled_dev, out_dev);
@@ -418,7 +429,8 @@ extern "C" int cpx_group_mean_finalize(cpx_ctx* ctx, const double* sum_dev,
 }
 
 extern "C" int cpx_nancorr(cpx_ctx* ctx, const double* mat_dev, int N, int K, double* out_dev) {
-  CPX_REQUIRE(ctx && mat_dev && out_dev && N >= 0 && N <= 8192 && K > 0 && K <= 65536,
+  // N == 0 (an empty matrix has no storage): every correlation is NaN, as pandas
+  CPX_REQUIRE(ctx && (mat_dev || N == 0) && out_dev && N >= 0 && N <= 8192 && K > 0 && K <= 65536,
               CPX_ERR_ARG, "cpx_nancorr: bad argument (N <= 8192 rows)");
   const long long npairs = (long long)K * (K + 1) / 2;
   hipLaunchKernelGGL(k_nancorr, dim3(cpx_div_up(npairs, kST)), dim3(kST),
@@ -430,8 +442,9 @@ extern "C" int cpx_nancorr(cpx_ctx* ctx, const double* mat_dev, int N, int K, do
 extern "C" int cpx_robust_mad(cpx_ctx* ctx, const double* mat_dev, int N, int K,
                               const int32_t* fit_rows_dev, int n_fit, double scale,
                               double* med_dev, double* mad_dev) {
-  CPX_REQUIRE(ctx && mat_dev && fit_rows_dev && med_dev && mad_dev && K > 0 && n_fit >= 0 &&
-                  n_fit <= kSortMax && K <= 2147483647,
+  // no fit rows (an empty index has no storage): median and MAD are NaN, as pandas / scipy
+  CPX_REQUIRE(ctx && mat_dev && (fit_rows_dev || n_fit == 0) && med_dev && mad_dev && K > 0 &&
+                  n_fit >= 0 && n_fit <= kSortMax && K <= 2147483647,
               CPX_ERR_ARG, "cpx_robust_mad: bad argument (at most %d fit rows)", kSortMax);
   hipLaunchKernelGGL(k_robust_mad, dim3(K), dim3(kST), 0, ctx->stream, mat_dev, N,
                      (const int*)fit_rows_dev, n_fit, scale, med_dev, mad_dev);

@@ -219,12 +219,15 @@ int cpx_group_mean_finalize(cpx_ctx* ctx, const double* sum_dev, const int64_t* 
                             int K, double* out_dev);
 
 /* pandas DataFrame.corr(method="pearson") (pycytominer correlation_threshold,
- * Pycyto_pertime.py:93-104): mat_dev column-major [K][N] (N <= 8192), out_dev [K][K].         */
+ * Pycyto_pertime.py:93-104): mat_dev column-major [K][N] (N <= 8192), out_dev [K][K].
+ * N == 0 (mat_dev may be NULL): all NaN.                                                       */
 int cpx_nancorr(cpx_ctx* ctx, const double* mat_dev, int N, int K, double* out_dev);
 
 /* pycytominer RobustMAD.fit (normalize(method="mad_robustize"), Pycyto_pertime.py:83-88):
  * per column of mat_dev (column-major [K][N]) over the rows fit_rows_dev[n_fit] (n_fit <= 4096):
- * med = median of the non-NaN values, mad = median(|x - med|) / scale (scale = 1/1.4826).     */
+ * med = median of the non-NaN values, mad = median(|x - med|) / scale (scale = 1/1.4826).
+ * As scipy, mad is NaN when med is NaN, or infinite and equal to one of the values (inf - inf
+ * among the deviations).  n_fit == 0 (fit_rows_dev may be NULL): med = mad = NaN.               */
 int cpx_robust_mad(cpx_ctx* ctx, const double* mat_dev, int N, int K, const int32_t* fit_rows_dev,
                    int n_fit, double scale, double* med_dev, double* mad_dev);
 

@@ -26,7 +26,8 @@ Numeric kernels restated here (the GPU kernels of k_profiles.hip do the same ari
   * `robust_mad_fit`: pycytominer RobustMAD.fit: median = pandas median (NaN skipped; even n:
     (a + b) / 2 of the two middle values, numpy's median), mad = scipy
     `median_abs_deviation(X, nan_policy="omit", scale=1/1.4826)` = median(|x - median|) /
-    (1/1.4826).  Pinned to pandas/scipy; the pycytominer wrapper itself (absent from this
+    (1/1.4826); NaN when the median is infinite and a value equals it (scipy: inf - inf = NaN
+    among the deviations) or is NaN.  Pinned to pandas/scipy; the pycytominer wrapper itself (absent from this
     image, unpinned in the reference's requirements.txt) is restated from its published
     source — parity of the composition is unpinned.
   * transform: (x - median) / (mad + 1e-18); double_sigmoid(x) = (x/alpha)**3 /
@@ -71,9 +72,10 @@ def group_kahan_mean(values: np.ndarray, group: np.ndarray, n_groups: int) -> np
             continue
         v = values[i]
         ok = ~np.isnan(v)
-        y = v - comp[g]
-        t = sumx[g] + y
-        c = (t - sumx[g]) - y
+        with np.errstate(invalid="ignore"):   # inf - inf after an infinite value
+            y = v - comp[g]
+            t = sumx[g] + y
+            c = (t - sumx[g]) - y
         c = np.where(np.isnan(c), 0.0, c)
         comp[g] = np.where(ok, c, comp[g])
         sumx[g] = np.where(ok, t, sumx[g])
@@ -122,7 +124,8 @@ def median_1d(x: np.ndarray) -> float:
         return math.nan
     if n % 2:
         return float(x[n // 2])
-    return float((x[n // 2 - 1] + x[n // 2]) / 2.0)
+    with np.errstate(invalid="ignore", over="ignore"):   # (-inf + inf) / 2 = NaN, overflow = inf
+        return float((x[n // 2 - 1] + x[n // 2]) / 2.0)
 
 
 def robust_mad_fit(X_fit: np.ndarray):
@@ -136,7 +139,11 @@ def robust_mad_fit(X_fit: np.ndarray):
         col = col[~np.isnan(col)]
         m = median_1d(col)
         med[j] = m
-        mad[j] = median_1d(np.abs(col - m)) / MAD_SCALE if len(col) else math.nan
+        with np.errstate(invalid="ignore"):
+            dev = np.abs(col - m)
+        # an infinite median leaves inf - inf = NaN among the deviations, and np.median (scipy,
+        # after omitting the NaN *inputs*) of an array that holds NaN is NaN
+        mad[j] = math.nan if np.isnan(dev).any() else median_1d(dev) / MAD_SCALE
     return med, mad
 
 

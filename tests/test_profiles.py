@@ -55,6 +55,25 @@ def test_oracle_robust_mad_is_pandas_scipy():
         assert np.array_equal(med, pd.DataFrame(X).median().to_numpy(), equal_nan=True)
         ref = median_abs_deviation(X, nan_policy="omit", scale=1 / 1.4826)
         assert np.array_equal(mad, ref, equal_nan=True)
+    # +-inf among the fit rows: a median of +-inf leaves inf - inf = NaN among scipy's deviations,
+    # so the MAD is NaN whatever the row order; an overflowed median of finite values gives inf
+    import warnings
+    inf = np.inf
+    cases = {(1, inf, inf, inf, 2): (inf, np.nan), (inf, inf, 1, 2, 3, inf, inf): (inf, np.nan),
+             (-inf, -inf, -inf, 1, 2): (-inf, np.nan), (2, 1, -inf, -inf, -inf): (-inf, np.nan),
+             (1, 2, inf, inf): (inf, np.nan), (-inf, inf, -inf, inf): (np.nan, np.nan),
+             (1, inf, 2, 3, -inf, 4, 5): (3.0, 2.0 / po.MAD_SCALE),
+             (1.5e308, 1.0, 1.6e308, 1.7e308): (inf, inf)}
+    for x, (med_exp, mad_exp) in cases.items():
+        X = np.array(x, dtype=np.float64)[:, None]
+        med, mad = po.robust_mad_fit(X)
+        with warnings.catch_warnings(), np.errstate(all="ignore"):
+            warnings.simplefilter("ignore")
+            med_ref = pd.DataFrame(X).median().to_numpy()
+            mad_ref = median_abs_deviation(X, nan_policy="omit", scale=1 / 1.4826)
+        assert np.array_equal(med, med_ref, equal_nan=True), x
+        assert np.array_equal(mad, mad_ref, equal_nan=True), x
+        assert np.array_equal([med[0], mad[0]], [med_exp, mad_exp], equal_nan=True), x
 
 
 def test_oracle_cosine_matches_sklearn():
