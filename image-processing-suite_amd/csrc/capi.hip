@@ -120,6 +120,9 @@ int cpx_debug_seg_timing(cpx_ctx* ctx, int enable) {
   if (enable && !ctx->seg_ev[0][0])
     for (int i = 0; i < cpx_ctx::kSegEv; ++i)
       for (int k = 0; k < 4; ++k) CPX_CHECK_HIP(hipEventCreate(&ctx->seg_ev[i][k]));
+  // slots still recorded hold asynchronous copies into seg_cnt[] that the next calls' slots
+  // (numbered from 0 again) would overwrite or free: wait for them before the reset
+  for (int i = 0; i < ctx->seg_nev; ++i) CPX_CHECK_HIP(hipEventSynchronize(ctx->seg_ev[i][3]));
   ctx->seg_timing = enable ? 1 : 0;
   ctx->seg_nev = 0;
   return CPX_OK;

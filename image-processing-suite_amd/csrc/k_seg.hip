@@ -420,20 +420,35 @@ struct FollowItem {
   int pad;
 };
 
-// NI items per thread (items i0 + j kT + t, j < NI): NI independent trajectories per lane, all
-// their gathers issued before any is used, so a wave keeps NI times the gathers in flight (the
-// kernel is bound by the latency of each trajectory's dependent gather chain, not by issue).
-// Per item the arithmetic and the order of the next round's list are those of NI = 1.
+// 16 bytes of gathered field in four consecutive VGPRs
+typedef float FollowQuad __attribute__((ext_vector_type(4)));
+
+// NI items per thread (items i0 + j kT + t, j < NI): NI independent trajectories per lane.  A
+// step runs in three phases — every item's cell and offsets; the loads of every item whose cell
+// changed; the arithmetic — and the loaded registers are first read behind the last item's
+// loads, so a wave has 2 NI gathers in flight and waits once per step.  Per item the arithmetic
+// and the order of the next round's list are those of NI = 1.  The nearer roof is VALU issue
+// (about 60 instructions per item-step, 32 of them fp64), not the return of the gathers
+// (DESIGN.md §4, §11.2).  NI = 2, V4: 64 VGPRs, 8 waves per SIMD.
 // V4: the two horizontal neighbours of a row in one 16-byte load (two gathers per step instead
-// of four; the gathers' address processing, not their bytes, bounds the kernel): (x0, x0 + 1),
-// or at the right edge (x0 - 1, x0) with the upper half taken for both.
+// of four): (x0, x0 + 1), or at the right edge (x0 - 1, x0) with the upper half taken for both.
+// Settings of the sweep in DESIGN.md §4 (tools/build_variants.sh compiles the others)
+#ifndef CPX_FOLLOW_NI
+#define CPX_FOLLOW_NI 2     // trajectories per thread
+#endif
+#ifndef CPX_FOLLOW_K0
+#define CPX_FOLLOW_K0 16    // steps per round while most pixels still move
+#endif
+#ifndef CPX_FOLLOW_WAVES
+#define CPX_FOLLOW_WAVES 8  // waves per SIMD the paired kernel's registers are held to
+#endif
+
 template <int NI, bool V4>
-__global__ __launch_bounds__(kT) void k_dyn_follow(int Dy, int Dx, int niter, int step0, int K,
-                                                   int from_act, const FollowItem* __restrict__ in,
-                                                   const int* __restrict__ in_cnt,
-                                                   FollowItem* __restrict__ out,
-                                                   int* __restrict__ out_cnt, DynBufs d) {
+__global__ __launch_bounds__(kT, V4 ? CPX_FOLLOW_WAVES : 1) void k_dyn_follow(
+    int Dy, int Dx, int niter, int step0, int K, int from_act, const FollowItem* __restrict__ in,
+    const int* __restrict__ in_cnt, FollowItem* __restrict__ out, int* __restrict__ out_cnt, DynBufs d) {
   const int fov = blockIdx.y;
+  const int bx = blockIdx.x, nbx = gridDim.x;
   const long long n = (long long)Dy * Dx;
   const int n_moving = d.st[fov].n_moving;
   if (n_moving < 5) return;  // follow_flows returns inds=None -> no masks
@@ -444,6 +459,8 @@ __global__ __launch_bounds__(kT) void k_dyn_follow(int Dy, int Dx, int niter, in
   const FollowItem* src = in + (long long)fov * n;
   FollowItem* dst = out + (long long)fov * n;
   const float fLy = (float)(Dy - 1), fLx = (float)(Dx - 1);
+  const int Dym1 = Dy - 1, Dxm1 = Dx - 1;
+  const unsigned int Dx8 = 8u * (unsigned int)Dx;
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int Dxh = Dx + 2 * kRpad;
   int* Hh = d.h + (long long)fov * (Dy + 2 * kRpad) * Dxh;
@@ -454,10 +471,13 @@ __global__ __launch_bounds__(kT) void k_dyn_follow(int Dy, int Dx, int niter, in
   (void)rsI;
   __shared__ int wsum[NI][kT / 64];
   __shared__ int sbase;
-  for (int i0 = blockIdx.x * kT * NI; i0 < n_in; i0 += gridDim.x * kT * NI) {  // block-uniform
-    bool active[NI], done[NI];
+  for (int i0 = bx * kT * NI; i0 < n_in; i0 += nbx * kT * NI) {  // block-uniform
+    bool active[NI];
     int q[NI];
     float py[NI], px[NI];
+    // the lanes whose item j still moves, as a wave mask (scalar registers: no vector
+    // instruction keeps it): all active items before the first step
+    unsigned long long moving[NI], act[NI];
 #pragma unroll
     for (int j = 0; j < NI; ++j) {
       const int i = i0 + j * kT + threadIdx.x;
@@ -477,66 +497,111 @@ __global__ __launch_bounds__(kT) void k_dyn_follow(int Dy, int Dx, int niter, in
           px[j] = it.px;
         }
       }
-      done[j] = !active[j];
+      act[j] = moving[j] = __ballot(active[j]);
     }
-    // the cell (integer position) of each item's last gathers and their values: a step that
-    // stays in the same cell — most of them once a trajectory slows near its sink — reuses them
-    // instead of gathering again (the field is read-only here: the same values, bit-identical)
-    float2 af[NI], bf[NI], cf[NI], ef[NI];
-    int cy[NI], cx[NI];
+    // each item's last gathers, kept raw (V4: r0 = the upper row's 16 bytes, r1 = the lower
+    // row's; scalar path: r0 = (a, b), r1 = (c, e)), and the byte offset of their cell: a step
+    // that stays in the same cell — most of them once a trajectory slows near its sink — reuses
+    // them instead of gathering again (the field is read-only here: the same values,
+    // bit-identical).  The offset names the cell: positions are clamped to the plane.
+    FollowQuad r0[NI], r1[NI];
+    unsigned int cb[NI];
 #pragma unroll
     for (int j = 0; j < NI; ++j) {
-      cy[j] = -1;
-      cx[j] = -1;
-      af[j] = bf[j] = cf[j] = ef[j] = make_float2(0.0f, 0.0f);
+      cb[j] = 0xffffffffu;
+      r0[j] = r1[j] = FollowQuad{0.0f, 0.0f, 0.0f, 0.0f};
     }
     for (int s = 0; s < steps; ++s) {
-      bool all = true;
+      // the wave leaves when none of its items moves (a lane whose items have all stopped runs
+      // along: a stopped item stays in its cell, so it gathers nothing, and finds its fixed
+      // point again)
+      unsigned long long any = 0;
 #pragma unroll
-      for (int j = 0; j < NI; ++j) all = all && done[j];
-      if (all) break;
-      // every item's gathers first (a finished item keeps its cell: no gather, its update is
-      // discarded below)
+      for (int j = 0; j < NI; ++j) any |= moving[j];
+      if (any == 0) break;
+      // phase 1: every item's cell, whether it changed, and the offsets of its two gathers.
+      // 32-bit byte offsets from the FOV's (block-uniform) field base: SGPR-base + VGPR-offset
+      // loads, no 64-bit address arithmetic per step (the field is < 4 GiB per FOV)
       int yi[NI], xi[NI];
+      unsigned int o0[NI], o1[NI];
+      bool changed[NI], redge[NI];
 #pragma unroll
       for (int j = 0; j < NI; ++j) {
         yi[j] = (int)py[j];
         xi[j] = (int)px[j];
-        if (yi[j] == cy[j] && xi[j] == cx[j]) continue;
-        cy[j] = yi[j];
-        cx[j] = xi[j];
-        const int y0 = min(Dy - 1, max(0, yi[j])), x0 = min(Dx - 1, max(0, xi[j]));
-        // 32-bit byte offsets from the FOV's (block-uniform) field base: SGPR-base + VGPR-offset
-        // loads, no 64-bit address arithmetic per step (the field is < 4 GiB per FOV)
-        const unsigned int b00 = 8u * (unsigned int)(y0 * Dx + x0);
-        const unsigned int bdx = x0 + 1 < Dx ? 8u : 0u, bdy = y0 + 1 < Dy ? 8u * (unsigned int)Dx : 0u;
+        unsigned int b00;
+        int y0 = yi[j], x0 = xi[j];
+        if constexpr (V4) {
+          // py, px come out of v_med3_f32 (or from pixel coordinates), so the cell is inside the
+          // plane, and the buffer load is range-checked: no clamps.  Dy, Dx <= 2^24 (host)
+          b00 = 8u * (__umul24((unsigned int)y0, (unsigned int)Dx) + (unsigned int)x0);
+        } else {
+          y0 = min(Dy - 1, max(0, y0));
+          x0 = min(Dx - 1, max(0, x0));
+          b00 = 8u * (unsigned int)(y0 * Dx + x0);
+        }
+        changed[j] = b00 != cb[j];
+        cb[j] = b00;
+        redge[j] = x0 >= Dxm1;
+        // the clamped neighbours are the pixel itself: at the right edge (x0 - 1, x0) is loaded
+        // (x0 = Dx - 1 >= 1) and phase 3 takes the upper half for both taps; in the last row the
+        // lower row is the upper one
+        o0[j] = (V4 && redge[j]) ? b00 - 8u : b00;
+        o1[j] = y0 < Dym1 ? o0[j] + Dx8 : o0[j];
+      }
+      // phase 2: the loads of every item whose cell changed, into the raw quads; nothing in
+      // these blocks reads them, so all NI items' gathers are in flight together
+#pragma unroll
+      for (int j = 0; j < NI; ++j) {
+        if (!changed[j]) continue;
         if constexpr (V4) {
           // raw buffer loads: one 16-byte access each (a plain float4 load of an 8-byte aligned
           // address is split into two 8-byte loads by the compiler)
-          const unsigned int o = bdx ? b00 : b00 - 8u;  // x0 = Dx - 1 >= 1 when bdx == 0
-          const float4 r0 = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsI, o, 0, 0));
-          const float4 r1 = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rsI, o + bdy, 0, 0));
-          af[j] = bdx ? make_float2(r0.x, r0.y) : make_float2(r0.z, r0.w);
-          bf[j] = make_float2(r0.z, r0.w);
-          cf[j] = bdx ? make_float2(r1.x, r1.y) : make_float2(r1.z, r1.w);
-          ef[j] = make_float2(r1.z, r1.w);
+          r0[j] = __builtin_bit_cast(FollowQuad, __builtin_amdgcn_raw_buffer_load_b128(rsI, o0[j], 0, 0));
+          r1[j] = __builtin_bit_cast(FollowQuad, __builtin_amdgcn_raw_buffer_load_b128(rsI, o1[j], 0, 0));
         } else {
-          af[j] = *reinterpret_cast<const float2*>(Ib + b00);
-          bf[j] = *reinterpret_cast<const float2*>(Ib + (b00 + bdx));
-          cf[j] = *reinterpret_cast<const float2*>(Ib + (b00 + bdy));
-          ef[j] = *reinterpret_cast<const float2*>(Ib + (b00 + bdy + bdx));
+          const unsigned int bdx = redge[j] ? 0u : 8u;
+          const float2 a = *reinterpret_cast<const float2*>(Ib + o0[j]);
+          const float2 b = *reinterpret_cast<const float2*>(Ib + (o0[j] + bdx));
+          const float2 c = *reinterpret_cast<const float2*>(Ib + o1[j]);
+          const float2 e = *reinterpret_cast<const float2*>(Ib + (o1[j] + bdx));
+          r0[j] = FollowQuad{a.x, a.y, b.x, b.y};
+          r1[j] = FollowQuad{c.x, c.y, e.x, e.y};
         }
       }
+      // the quads pass this point as whole registers: their first use, and with it the wait
+      // for the loads, stands behind the last item's loads
+#pragma unroll
+      for (int j = 0; j < NI; ++j) asm volatile("" : "+v"(r0[j]), "+v"(r1[j]));
+      // phase 3: taps, weights, update
 #pragma unroll
       for (int j = 0; j < NI; ++j) {
-        const double2 a = {(double)af[j].x, (double)af[j].y}, b = {(double)bf[j].x, (double)bf[j].y},
-                      c = {(double)cf[j].x, (double)cf[j].y}, e = {(double)ef[j].x, (double)ef[j].y};
+        if constexpr (V4) {
+          // right edge: the upper half is both taps, written over the lower half in place (the
+          // quad belongs to this cell until the next gather; doing it again changes nothing).
+          // Few waves have a lane there: one scalar branch, taken by those alone.
+          // (px >= Dx - 1 is the cell test x0 >= Dx - 1: px <= Dx - 1 <= 2^24, exact in fp32;
+          // a comparison of its own, so that the wave mask comes straight out of it)
+          if (__builtin_amdgcn_ballot_w64(px[j] >= fLx) != 0) {
+            asm volatile("" : "+v"(r0[j]), "+v"(r1[j]));  // (keeps the branch: not four selects)
+            if (px[j] >= fLx) {
+              r0[j].x = r0[j].z;
+              r0[j].y = r0[j].w;
+              r1[j].x = r1[j].z;
+              r1[j].y = r1[j].w;
+            }
+          }
+        }
+        const double2 a = {(double)r0[j].x, (double)r0[j].y}, b = {(double)r0[j].z, (double)r0[j].w},
+                      c = {(double)r1[j].x, (double)r1[j].y}, e = {(double)r1[j].z, (double)r1[j].w};
         double vy, vx;
         if (py[j] >= 1.0f && px[j] >= 1.0f) {
           // yy = frac(py) and 1 - yy are exact in fp32 (multiples of 2^-23 in [0, 1]), so
           // I * (1 - yy) is exact in fp64 and (I * (1 - yy)) * (1 - xx) == I * w00 with
-          // w00 = (1 - yy) * (1 - xx) exact: the same single rounding, four fewer multiplies
-          const float yf = py[j] - (float)yi[j], xf = px[j] - (float)xi[j];
+          // w00 = (1 - yy) * (1 - xx) exact: the same single rounding, four fewer multiplies.
+          // py - (float)(int)py is exact too, so v_fract_f32 gives the same bits in one
+          // instruction
+          const float yf = __builtin_amdgcn_fractf(py[j]), xf = __builtin_amdgcn_fractf(px[j]);
           const double y1 = (double)yf, x1 = (double)xf, y0d = (double)(1.0f - yf), x0d = (double)(1.0f - xf);
           const double w00 = y0d * x0d, w01 = y0d * x1, w10 = y1 * x0d, w11 = y1 * x1;
           vy = a.x * w00 + b.x * w01 + c.x * w10 + e.x * w11;
@@ -549,13 +614,19 @@ __global__ __launch_bounds__(kT) void k_dyn_follow(int Dy, int Dx, int niter, in
         // clamp to [0, L - 1] in one v_med3_f32 (= fminf(L, fmaxf(0, .)) for the finite values here)
         const float ny = __builtin_amdgcn_fmed3f(py[j] + (float)vy, 0.0f, fLy);
         const float nx = __builtin_amdgcn_fmed3f(px[j] + (float)vx, 0.0f, fLx);
-        if (!done[j]) {
-          if (ny == py[j] && nx == px[j]) done[j] = true;  // exact fixed point
-          py[j] = ny;
-          px[j] = nx;
-        }
+        // the update depends on the position alone, so an item on its exact fixed point finds
+        // it again at every later step: `moving` is this step's comparison, nothing to carry
+        // per lane, and storing the unchanged position changes nothing
+        // (the builtin takes a comparison's mask as it is; __ballot converts it to an int first)
+        moving[j] = (__builtin_amdgcn_ballot_w64(ny != py[j]) | __builtin_amdgcn_ballot_w64(nx != px[j])) &
+                    act[j];
+        py[j] = ny;
+        px[j] = nx;
       }
     }
+    bool done[NI];
+#pragma unroll
+    for (int j = 0; j < NI; ++j) done[j] = !((moving[j] >> lane) & 1ull);
     const bool last = step0 + steps >= niter;
     bool carry[NI];
     unsigned long long bal[NI];
@@ -593,7 +664,10 @@ __global__ __launch_bounds__(kT) void k_dyn_follow(int Dy, int Dx, int niter, in
         it.py = py[j];
         it.px = px[j];
         it.pad = 0;
-        dst[sbase + wsum[j][wid] + __popcll(bal[j] & ((1ull << lane) - 1ull))] = it;
+        // rank among the wave's carried lanes: v_mbcnt counts the mask's bits below the lane
+        const int below = (int)__builtin_amdgcn_mbcnt_hi((unsigned int)(bal[j] >> 32),
+                                                         __builtin_amdgcn_mbcnt_lo((unsigned int)bal[j], 0u));
+        dst[sbase + wsum[j][wid] + below] = it;
       }
     __syncthreads();
   }
@@ -2536,7 +2610,7 @@ extern "C" int cpx_seg_masks(cpx_ctx* ctx, const float* yf_dev, int B, const cpx
   const size_t sz_small = al(sizeof(int) * (size_t)B);
   // follow rounds: K = k0 steps while most pixels still move (until step sw), then k1 for the
   // long tail (k0 = 24 / 32 / 48 measured equal to 16, `gpurun_out/r06af`)
-  constexpr int k0 = 16, sw = 384, k1 = 128;
+  constexpr int k0 = CPX_FOLLOW_K0, sw = 384, k1 = 128;
   const int rounds = cpx_div_up(sw, k0) + cpx_div_up(std::max(0, niter - sw), k1) + 2;
   const size_t sz_fcnt = al(sizeof(int) * (size_t)B * (rounds + 1));
   const size_t sz_items = al((size_t)16 * B * n);
@@ -2590,7 +2664,9 @@ extern "C" int cpx_seg_masks(cpx_ctx* ctx, const float* yf_dev, int B, const cpx
   // k_dyn_follow: two trajectories per thread and paired 16-byte gathers; per 48-FOV step
   // (`gpurun_out/r05l`, `r05m`, trajectories / gathers): 1 / scalar 12.11 ms, 2 / scalar 11.83,
   // 4 / scalar 12.54, 1 / paired 11.46, 2 / paired 11.02 (kept); every setting passed the
-  // segmentation parity tests
+  // segmentation parity tests.  On the three-phase step loop (`profiles/r08a_follow_sweep.txt`,
+  // the whole call per 48 FOVs): 2 trajectories 24.7 ms with k0 16 or 32, at 7 or 8 waves alike;
+  // 3 trajectories (122 VGPRs) 30.7; 4 (188 VGPRs) 38.6; a FOV's blocks on one XCD 25.3
   // (development / bench instrumentation: cpx_debug_seg_timing)
   const int sev = ctx->seg_timing && ctx->seg_nev < cpx_ctx::kSegEv ? ctx->seg_nev++ : -1;
   bool fe_timed = false;  // the register flow-error kernels were bracketed (else a zero interval)
@@ -2602,9 +2678,10 @@ extern "C" int cpx_seg_masks(cpx_ctx* ctx, const float* yf_dev, int B, const cpx
       const int K = step < sw ? k0 : k1;
       const FollowItem* in = (const FollowItem*)(r & 1 ? d.fitems1 : d.fitems0);
       FollowItem* out = (FollowItem*)(r & 1 ? d.fitems0 : d.fitems1);
-      // (the right-edge form reads x0 - 1; the buffer resource holds 8 n < 2^31 bytes)
-      const bool v4 = Dx >= 2 && 8LL * n < (1LL << 31);
-      auto kern = v4 ? k_dyn_follow<2, true> : k_dyn_follow<2, false>;
+      // (the right-edge form reads x0 - 1; the buffer resource holds 8 n < 2^31 bytes;
+      // and the cell's offset is a 24-bit multiply)
+      const bool v4 = Dx >= 2 && 8LL * n < (1LL << 31) && Dy <= (1 << 24) && Dx <= (1 << 24);
+      auto kern = v4 ? k_dyn_follow<CPX_FOLLOW_NI, true> : k_dyn_follow<2, false>;
       hipLaunchKernelGGL(kern, dim3(fblk, B), dim3(kT), 0, ctx->stream, Dy, Dx, niter, step, K,
                          r == 0 ? 1 : 0, in, (const int*)(d.fcnt + (size_t)B * r), out,
                          d.fcnt + (size_t)B * (r + 1), d);

@@ -27,7 +27,8 @@ def main():
         m = sum(c[k] for c in calls) / len(calls)
         tot += m
         print(f"round {k:2d}: {m:8.1f} us")
-    print(f"per call: {tot:.1f} us over {len(calls)} calls")
+    sums = [sum(c) for c in calls]
+    print(f"per call: {tot:.1f} us over {len(calls)} calls (per-call sums {min(sums):.1f} .. {max(sums):.1f} us)")
 
 
 if __name__ == "__main__":
