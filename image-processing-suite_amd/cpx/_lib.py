@@ -31,6 +31,12 @@ COLOC_MAX_CHANNELS = 8
 N_IEXT = 14             # intensity-extension columns per channel (CPX_N_IEXT)
 IEXT_LDS_PIXELS = 9216  # largest object cpx_intensity_ext selects from LDS (CPX_IEXT_LDS_PIXELS)
 N_HAR = 9               # Haralick columns per channel and direction (CPX_N_HAR)
+N_NEIGHBORS = 7         # neighbour columns per scale (CPX_N_NEIGHBORS)
+NEIGHBORS_MAX_DISTANCE = 32  # CPX_NEIGHBORS_MAX_DISTANCE
+NEIGHBORS_MAX_SCALES = 4     # CPX_NEIGHBORS_MAX_SCALES
+NEIGHBORS_BAND_ROWS = 64     # core rows of the touch kernel's tile (CPX_NEIGHBORS_BAND_ROWS)
+NEIGHBORS_SEGMENT_COLS = 64  # core columns of that tile (CPX_NEIGHBORS_SEGMENT_COLS)
+NEIGHBORS_MAX_LABEL = 131071  # CPX_NEIGHBORS_MAX_LABEL
 
 
 class CpxError(RuntimeError):
@@ -115,6 +121,8 @@ SIGNATURES = {
     "cpx_intensity_ext": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "cpx_n_texture_haralick": (_I, [_I]),
     "cpx_texture_haralick": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "cpx_n_neighbors": (_I, [_I]),
+    "cpx_neighbors": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P]),
     "cpx_csv_format": (_I64, [_I64, _I64, _I, _P, _P, _P, _P, _I64]),
     "cpx_debug_glcm_timing": (_I, [_P, _I]),
     "cpx_debug_glcm_ms": (_I, [_P, ct.POINTER(ct.c_double), ct.POINTER(_I)]),
@@ -150,6 +158,7 @@ SIGNATURES = {
     "cpx_fov_colocalization": (_I, [_P, _P, _I, ct.c_double, _P, _P]),
     "cpx_fov_intensity_ext": (_I, [_P, _P, _I, _P, _P]),
     "cpx_fov_texture_haralick": (_I, [_P, _P, _I, _P, _P]),
+    "cpx_fov_neighbors": (_I, [_P, _P, _I, _P, _I, _P, _P]),
     "cpx_fov_wait": (_I, [_P]),
     "cpx_cpnet_conv3x3": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _I]),
     "cpx_cpnet_conv3x3_head": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P,

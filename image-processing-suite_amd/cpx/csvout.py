@@ -15,6 +15,8 @@ writes those four tables from the GPU pipeline's results:
                  and Location_MaxIntensity_* per channel)
                  and, with texture_haralick=True, of `haralick_names(channels)` (the nine Haralick
                  Texture_* columns the feature block lacks, per channel and direction)
+                 and, with neighbors=(scales), of `neighbors_names(scales)` (Neighbors_<F>_<S>,
+                 seven per scale, S = Adjacent or the distance)
 ImageNumber is the 1-based LoadData row; ObjectNumber is the object's label, which the
 segmentation makes consecutive (1..K per image) and which Cells and Cytoplasm share with their
 nucleus.  Rows are sorted by (ImageNumber, ObjectNumber), so the output does not depend on the
@@ -176,6 +178,18 @@ def haralick_names(channels):
             for n in HARALICK_NAMES]
 
 
+# in the order of include/cpx.h CPX_NB_*
+NEIGHBORS_NAMES = ["NumberOfNeighbors", "PercentTouching", "FirstClosestObjectNumber", "FirstClosestDistance",
+                   "SecondClosestObjectNumber", "SecondClosestDistance", "AngleBetweenNeighbors"]
+
+
+def neighbors_names(scales):
+    """Column names of a cpx_neighbors row: Neighbors_<F>_<S>, seven per scale, scale-major; S is
+    Adjacent for the scale given as "Adjacent" and the decimal distance otherwise."""
+    tags = ["Adjacent" if isinstance(s, str) and s.lower() == "adjacent" else str(int(s)) for s in scales]
+    return [f"Neighbors_{n}_{t}" for t in tags for n in NEIGHBORS_NAMES]
+
+
 class _TableStream:
     """Appends formatted CSV blocks to one file on a writer thread, in arrival order, while their
     ImageNumbers increase; finish() reports whether the file is complete and ordered."""
@@ -243,7 +257,8 @@ class PlateTables:
     """Accumulates per-FOV results of one plate/time and writes the four CSVs."""
 
     def __init__(self, channels, eager_csv: bool = False, stream_dir: str | None = None,
-                 colocalization: bool = False, intensity_ext: bool = False, texture_haralick: bool = False):
+                 colocalization: bool = False, intensity_ext: bool = False, texture_haralick: bool = False,
+                 neighbors: tuple = ()):
         self.channels = list(channels)
         self.cols = feature_names(self.channels)
         if colocalization:  # rows carry the Correlation_* block after the features (cpx.pipeline)
@@ -252,6 +267,8 @@ class PlateTables:
             self.cols += intensity_ext_names(self.channels)
         if texture_haralick:  # ... then the Haralick texture block
             self.cols += haralick_names(self.channels)
+        if neighbors:         # ... then the Neighbors_* block, last
+            self.cols += neighbors_names(neighbors)
         self.images = []                       # dicts
         self.objects = {t: [] for t in OBJECT_TABLES}  # (ImageNumber, labels[n], feats[n, F])
         # eager_csv: each FOV's object rows are formatted on a thread pool as they are added

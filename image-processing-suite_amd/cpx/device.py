@@ -273,6 +273,17 @@ class Device:
                                             _ptr(objects), _ptr(hdr), _ptr(out)),
               "cpx_texture_haralick")
 
+    def neighbors(self, labels, max_label, objects, hdr, scales, out):
+        """cpx_neighbors: out float64 [B, max_label, n_neighbors(scales)], row k = the k-th object of
+        the table (rows >= n_objects untouched), column 7 * s + j; scales of "Adjacent" or int D."""
+        B, H, W = labels.shape
+        d = neighbors_distances(scales)
+        assert out.dtype == torch.float64 and out.numel() >= B * max_label * _lib.N_NEIGHBORS * len(d)
+        self._bind_stream()
+        check(self.lib.cpx_neighbors(self.h, _ptr(labels), B, H, W, max_label, _ptr(objects), _ptr(hdr),
+                                     (ct.c_int * max(len(d), 1))(*d), len(d), _ptr(out)),
+              "cpx_neighbors")
+
 
 # Pipeline streams with their own CUs (round 5): two pipelines whose streams each hold a CU mask
 # of one contiguous half of the GPU's CUs (hipExtStreamCreateWithCUMask) ran the bench 0.8-0.9 %
@@ -362,6 +373,18 @@ def n_intensity_ext(C: int) -> int:
 def n_texture_haralick(C: int) -> int:
     """Columns of a cpx_texture_haralick row (cpx_n_texture_haralick): 9 per channel and direction."""
     return 4 * _lib.N_HAR * C if C > 0 else 0
+
+
+def neighbors_distances(scales) -> list:
+    """The integer distance D of each neighbour scale: 1 for "Adjacent", else the int itself (the
+    range 1 .. NEIGHBORS_MAX_DISTANCE is checked by cpx_neighbors)."""
+    return [1 if isinstance(s, str) and s.lower() == "adjacent" else int(s) for s in scales]
+
+
+def n_neighbors(scales) -> int:
+    """Columns of a cpx_neighbors row (cpx_n_neighbors): 7 per scale; `scales` a sequence or a count."""
+    n = scales if isinstance(scales, int) else len(scales)
+    return _lib.N_NEIGHBORS * n if n > 0 else 0
 
 
 def as_numpy(t: torch.Tensor, kind: str):

@@ -15,7 +15,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import check
-from .device import n_colocalization, n_features, n_intensity_ext, n_texture_haralick
+from .device import (n_colocalization, n_features, n_intensity_ext, n_neighbors, n_texture_haralick,
+                     neighbors_distances)
 
 
 class FovSession:
@@ -147,6 +148,20 @@ class FovSession:
         check(self.lib.cpx_fov_texture_haralick(self.h, ct.c_void_p(lab.data_ptr()), max_objects,
                                                 out.ctypes.data_as(ct.c_void_p), ct.byref(n)),
               "cpx_fov_texture_haralick")
+        return out[: n.value].copy()
+
+    def neighbors(self, labels, scales, max_objects: int = 4096) -> np.ndarray:
+        """Neighbour rows [n_objects, n_neighbors(scales)] (NumberOfNeighbors, PercentTouching, the
+        two closest objects and the angle between them, per scale of "Adjacent" or int D) of the
+        objects of `labels` at the submitted FOV's shape (the same objects and order as features())."""
+        lab = self._labels(labels)
+        d = neighbors_distances(scales)
+        out = np.empty((max_objects, n_neighbors(len(d))), np.float64)
+        n = ct.c_int()
+        check(self.lib.cpx_fov_neighbors(self.h, ct.c_void_p(lab.data_ptr()), max_objects,
+                                         (ct.c_int * max(len(d), 1))(*d), len(d),
+                                         out.ctypes.data_as(ct.c_void_p), ct.byref(n)),
+              "cpx_fov_neighbors")
         return out[: n.value].copy()
 
     def _labels(self, labels):

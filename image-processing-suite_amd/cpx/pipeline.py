@@ -26,7 +26,7 @@ import torch
 
 from . import _lib
 from ._lib import COLOC_MAX_CHANNELS
-from .device import Device, as_numpy, n_colocalization, n_features, n_intensity_ext, n_texture_haralick
+from .device import Device, as_numpy, n_colocalization, n_features, n_intensity_ext, n_neighbors, n_texture_haralick
 from .segment import CELLPOSE_MODEL, DIAMETER, Segmenter
 
 OBJECT_SETS = ("Nuclei", "Cells", "Cytoplasm")
@@ -81,6 +81,9 @@ class PipelineConfig:
     texture_haralick: bool = False   # also measure the nine Haralick columns the Texture_* block
                                      # lacks (cpx_texture_haralick): n_texture_haralick(C) more
                                      # columns, after the blocks above
+    neighbors: tuple = ()            # neighbour scales, each "Adjacent" or an int distance D (at most
+                                     # 4, D within 1 .. 32): also measure the Neighbors_* block
+                                     # (cpx_neighbors), 7 columns per scale, after the blocks above
 
     def ws_channel(self) -> int:
         """The watershed elevation channel (cell_channel, or "AGP" / the last channel)."""
@@ -98,7 +101,8 @@ class FovResults:
     feats: dict                      # set -> list of float64 [n_objects, F] (F = n_features(C), plus
                                      # n_colocalization(C) with PipelineConfig.colocalization, plus
                                      # n_intensity_ext(C) with PipelineConfig.intensity_ext, plus
-                                     # n_texture_haralick(C) with PipelineConfig.texture_haralick)
+                                     # n_texture_haralick(C) with PipelineConfig.texture_haralick, plus
+                                     # n_neighbors(scales) with PipelineConfig.neighbors)
     seg_stats: np.ndarray
     failed: np.ndarray | None = None  # [B] bool: the FOV's Cells watershed did not converge even
                                       # after the re-runs with more rounds; its object tables are
@@ -164,6 +168,7 @@ class FovPipeline:
         self.K = n_colocalization(C) if cfg.colocalization else 0  # appended columns (0: none)
         self.X = n_intensity_ext(C) if cfg.intensity_ext else 0    # appended after those (0: none)
         self.T = n_texture_haralick(C) if cfg.texture_haralick else 0  # ... and after those
+        self.N = n_neighbors(tuple(cfg.neighbors))                     # ... and last (0: none)
         self.seg = Segmenter(dev, H, W, B, model=cfg.model, diameter=cfg.diameter, weights=cfg.weights,
                              seed=cfg.seed, use_graph=cfg.use_graph and cfg.cpnet_precision != "fp32",
                              max_objects=ML, resample=cfg.resample, precision=cfg.cpnet_precision)
@@ -187,6 +192,9 @@ class FovPipeline:
             if self.T:
                 self._slots[-1]["har"] = {s: torch.zeros((B, ML, self.T), dtype=torch.float64, device=td)
                                           for s in OBJECT_SETS}
+            if self.N:
+                self._slots[-1]["nbr"] = {s: torch.zeros((B, ML, self.N), dtype=torch.float64, device=td)
+                                          for s in OBJECT_SETS}
         self._host = {
             "qc": torch.empty(24 * B * C, dtype=torch.uint8, pin_memory=True),
             "hdr": {s: torch.empty(16 * B, dtype=torch.uint8, pin_memory=True) for s in OBJECT_SETS},
@@ -202,6 +210,9 @@ class FovPipeline:
                                   for s in OBJECT_SETS}
         if self.T:
             self._host["har"] = {s: torch.empty(B * ML * self.T, dtype=torch.float64, pin_memory=True)
+                                 for s in OBJECT_SETS}
+        if self.N:
+            self._host["nbr"] = {s: torch.empty(B * ML * self.N, dtype=torch.float64, pin_memory=True)
                                  for s in OBJECT_SETS}
         # one result-copy stream per device, shared by its pipelines: a process has only
         # GPU_MAX_HW_QUEUES (4) hardware queues, and streams beyond that share one, which
@@ -237,6 +248,7 @@ class FovPipeline:
         self.coloc = sl.get("coloc")
         self.iext = sl.get("iext")
         self.har = sl.get("har")
+        self.nbr = sl.get("nbr")
 
     # ---- stages ---------------------------------------------------------------------------
     # A stage in STAGE_EXCLUSIVE (of illum_qc, cpnet, seg_post, cells, features) of one pipeline
@@ -326,6 +338,10 @@ class FovPipeline:
             for s in OBJECT_SETS:
                 self.dev.texture_haralick(self.labels[s], self.corr, cfg.C, cfg.max_objects, self.objects[s],
                                           self.hdr[s], self.har[s])
+        if self.N:
+            for s in OBJECT_SETS:
+                self.dev.neighbors(self.labels[s], cfg.max_objects, self.objects[s], self.hdr[s],
+                                   tuple(cfg.neighbors), self.nbr[s])
         if self.cfg.crops:
             self.dev.objects(self.labels["Nuclei"], cfg.max_objects, cfg.box, self.lstats,
                              self.objects["Nuclei"], self.hdr["Nuclei"])
@@ -368,7 +384,7 @@ class FovPipeline:
         from .segment import SEG_ERR_INTERNAL, SEG_OVF_FILL_PARTIAL, SEG_OVF_SEEDS, SEG_STATS_DTYPE
         k = self.cur if slot is None else slot
         sl, hb = self._slots[k], self._host
-        B, ML, F, K, X, T = self.cfg.batch, self.cfg.max_objects, self.F, self.K, self.X, self.T
+        B, ML, F, K, X, T, N = self.cfg.batch, self.cfg.max_objects, self.F, self.K, self.X, self.T, self.N
         cs = self._copy_stream
         cs.wait_event(sl["event"])
         with torch.cuda.stream(cs):
@@ -416,6 +432,10 @@ class FovPipeline:
                     tg = sl["har"][s].view(B * ML, T).index_select(0, idx)
                     hb["har"][s][:tot * T].view(tot, T).copy_(tg, non_blocking=True)
                     keep.append(tg)
+                if N:
+                    ng = sl["nbr"][s].view(B * ML, N).index_select(0, idx)
+                    hb["nbr"][s][:tot * N].view(tot, N).copy_(ng, non_blocking=True)
+                    keep.append(ng)
         _sync_after(cs)
         del keep
         objs, feats = {}, {}
@@ -430,6 +450,8 @@ class FovPipeline:
                 f = np.concatenate([f, hb["iext"][s][:tot * X].view(tot, X).numpy()], axis=1)
             if T:  # ... then the Haralick texture block
                 f = np.concatenate([f, hb["har"][s][:tot * T].view(tot, T).numpy()], axis=1)
+            if N:  # ... then the Neighbors_* block
+                f = np.concatenate([f, hb["nbr"][s][:tot * N].view(tot, N).numpy()], axis=1)
             o = as_numpy(hb["objects"][s][:max(tot, 1) * 56], "object")[:tot]
             feats[s] = [f[off[b]:off[b + 1]].copy() for b in range(B)]
             objs[s] = [o[off[b]:off[b + 1]].copy() for b in range(B)]

@@ -111,7 +111,29 @@ def parse_args(argv=None):
                          "SumAverage, SumVariance, SumEntropy, Entropy, DifferenceVariance, DifferenceEntropy, "
                          "InfoMeas1, InfoMeas2 per channel and direction; PipelineConfig.texture_haralick) after "
                          "the columns above")
+    ap.add_argument("--neighbors", type=parse_neighbors, default=(), metavar="SCALES",
+                    help="also write the Neighbors_* columns (NumberOfNeighbors, PercentTouching, the two closest "
+                         "objects and the angle between them; PipelineConfig.neighbors) after the columns above, "
+                         "seven per scale of the comma-separated list, each Adjacent or a distance 1..32 in pixels, "
+                         "at most 4 (e.g. Adjacent,5)")
     return ap.parse_args(argv)
+
+
+def parse_neighbors(text: str) -> tuple:
+    """--neighbors Adjacent,5 -> ("Adjacent", 5)."""
+    from . import _lib
+    out = []
+    for tok in (t.strip() for t in text.split(",")):
+        if tok.lower() == "adjacent":
+            out.append("Adjacent")
+        elif tok.isdigit() and 1 <= int(tok) <= _lib.NEIGHBORS_MAX_DISTANCE:
+            out.append(int(tok))
+        else:
+            raise argparse.ArgumentTypeError(f"--neighbors: {tok!r} is neither Adjacent nor a distance within "
+                                             f"1..{_lib.NEIGHBORS_MAX_DISTANCE}")
+    if not 1 <= len(out) <= _lib.NEIGHBORS_MAX_SCALES:
+        raise argparse.ArgumentTypeError(f"--neighbors: 1..{_lib.NEIGHBORS_MAX_SCALES} scales")
+    return tuple(out)
 
 
 def shard_rows(table, rank: int, world: int):
@@ -281,7 +303,7 @@ def run(argv=None):
         out = PlateTables(chans, eager_csv=a.world == 1,
                           stream_dir=job_dir(a.out, plate, time) if a.world == 1 else None,
                           colocalization=a.colocalization, intensity_ext=a.intensity_extended,
-                          texture_haralick=a.texture_haralick)
+                          texture_haralick=a.texture_haralick, neighbors=a.neighbors)
         status = []  # per site: the reference's results_dict entry (Cellpose_GPU_s3fs.py:123-125,219-223)
         d = job_dir(a.out, plate, time)
         try:
@@ -375,7 +397,8 @@ def _run_sites(a, table, source, chans, state, out, status):
                              colocalization=bool(getattr(a, "colocalization", False)),
                              coloc_threshold=float(getattr(a, "colocalization_threshold", 15.0)),
                              intensity_ext=bool(getattr(a, "intensity_extended", False)),
-                             texture_haralick=bool(getattr(a, "texture_haralick", False)))
+                             texture_haralick=bool(getattr(a, "texture_haralick", False)),
+                             neighbors=tuple(getattr(a, "neighbors", ())))
         if a.ws_rounds:
             cfg.ws_rounds = tuple(a.ws_rounds)
         illum = _illum(a.illum_path, chans, H, W)

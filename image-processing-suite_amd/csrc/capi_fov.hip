@@ -40,6 +40,8 @@ struct cpx_fov_state {
   size_t iext_cap = 0;
   double* har = nullptr;      // [max_objects][cpx_n_texture_haralick(C)] (cpx_fov_texture_haralick)
   size_t har_cap = 0;
+  double* nbr = nullptr;      // [max_objects][cpx_n_neighbors(n_scales)] (cpx_fov_neighbors)
+  size_t nbr_cap = 0;
 };
 
 void cpx_fov_free(cpx_ctx* ctx) {
@@ -48,7 +50,7 @@ void cpx_fov_free(cpx_ctx* ctx) {
   for (void* p : f->illum)
     if (p) (void)hipFree(p);
   void* bufs[] = {f->raw, f->zplane, f->corr, f->stats, f->qc,
-                  f->lstats, f->objects, f->hdr, f->feats, f->yf, f->coloc, f->iext, f->har};
+                  f->lstats, f->objects, f->hdr, f->feats, f->yf, f->coloc, f->iext, f->har, f->nbr};
   for (void* p : bufs)
     if (p) (void)hipFree(p);
   delete f;
@@ -363,6 +365,30 @@ int cpx_fov_texture_haralick(cpx_ctx* ctx, const int32_t* labels_dev, int max_ob
     return rc;
   if (host_out && *n_out > 0) {
     CPX_CHECK_HIP(hipMemcpyAsync(host_out, f->har, sizeof(double) * K * (*n_out), hipMemcpyDeviceToHost,
+                                 ctx->stream));
+  }
+  CPX_CHECK_HIP(hipStreamSynchronize(ctx->stream));
+  return CPX_OK;
+}
+
+int cpx_fov_neighbors(cpx_ctx* ctx, const int32_t* labels_dev, int max_objects, const int* distances,
+                      int n_scales, double* host_out, int* n_out) {
+  CPX_REQUIRE(ctx && labels_dev && n_out && max_objects > 0, CPX_ERR_ARG, "cpx_fov_neighbors: bad argument");
+  CPX_REQUIRE(n_scales >= 1 && n_scales <= CPX_NEIGHBORS_MAX_SCALES, CPX_ERR_ARG,
+              "cpx_fov_neighbors: %d scales (1 .. %d supported)", n_scales, CPX_NEIGHBORS_MAX_SCALES);
+  CPX_REQUIRE(ctx->fov && ctx->fov->have, CPX_ERR_STATE, "cpx_fov_neighbors: no FOV submitted");
+  cpx_fov_state* f = ctx->fov;
+  int rc;
+  if ((rc = cpx_fov_object_table(ctx, labels_dev, 0, max_objects, nullptr, n_out)) != CPX_OK) return rc;
+  const size_t K = (size_t)cpx_n_neighbors(n_scales);
+  if ((rc = grow(ctx, (void**)&f->nbr, &f->nbr_cap, sizeof(double) * K * max_objects, "fov neighbours")) !=
+      CPX_OK)
+    return rc;
+  if ((rc = cpx_neighbors(ctx, labels_dev, 1, f->H, f->W, max_objects, f->objects, f->hdr, distances, n_scales,
+                          f->nbr)) != CPX_OK)
+    return rc;
+  if (host_out && *n_out > 0) {
+    CPX_CHECK_HIP(hipMemcpyAsync(host_out, f->nbr, sizeof(double) * K * (*n_out), hipMemcpyDeviceToHost,
                                  ctx->stream));
   }
   CPX_CHECK_HIP(hipStreamSynchronize(ctx->stream));

@@ -432,6 +432,68 @@ int cpx_texture_haralick(cpx_ctx* ctx, const int32_t* labels_dev, const float* c
                          int H, int W, int max_label, const cpx_object* objects_dev,
                          const cpx_fov_objects* hdr_dev, double* out_dev);
 
+/* ---- a10: per-object neighbour measurements (Neighbors_*) ----------------------------------- *
+ * CellProfiler 4 MeasureObjectNeighbors with an object set measured against itself, in the
+ * "Adjacent" (D = 1) and "Within a specified distance" (D) modes; "Expand until adjacent" is not
+ * covered.  Restated here, in DESIGN.md §15 and as numpy in tests/neighbors_ref.py.
+ *   labels: the plane; a value outside 1..max_label is background (as cpx_objects ignores it).
+ *   Objects in table order (ascending label), k = 0..n-1; object k has the pixel set P_k and the
+ *   centre c_k = (sum r / |P_k|, sum c / |P_k|) in float64 (exact integer sums, one division each:
+ *   the table's centroid_r / centroid_c).  E_k is the edge set of DESIGN §13: a pixel of P_k in
+ *   the plane's first or last row or column, or with one of its 8 neighbours of another label
+ *   (background included); never empty.  D is an integer, 1 <= D <= CPX_NEIGHBORS_MAX_DISTANCE.
+ *   NumberOfNeighbors   the number of distinct labels M not in {0, L} with a pixel q and a pixel
+ *                       p of P_L such that (q - p).(q - p) <= D^2 (dilation by strel_disk(D); at
+ *                       D = 1 the 4-neighbourhood, so a diagonal-only contact is no neighbour)
+ *   PercentTouching     (t * 100) / |E_L| in float64 (exact product, one division), t = the number
+ *                       of pixels p of E_L with a pixel q of a label not in {0, L} and
+ *                       (q - p).(q - p) <= D^2 + D (strel_disk(D + 0.5): the 3 x 3 at D = 1)
+ *   FirstClosestObjectNumber, FirstClosestDistance, SecondClosestObjectNumber,
+ *   SecondClosestDistance
+ *                       d(k, j) = sqrt((c_k.r - c_j.r)^2 + (c_k.c - c_j.c)^2) in float64, each
+ *                       square and the sum rounded on their own, the root correctly rounded; all
+ *                       j = 0..n-1, k included, ordered by (d, j) ascending (numpy's stable
+ *                       argsort); First and Second are ranks 1 and 2, reported as label and d.
+ *                       An earlier object with the same centre as k takes rank 0, and rank 1 is
+ *                       then k itself at distance 0 (CellProfiler's rule as written).
+ *   AngleBetweenNeighbors  with v1 = c_first - c_k, v2 = c_second - c_k:
+ *                       atan2(|v1.c v2.r - v1.r v2.c|, v1.v2) * 180 / pi, 0..180 degrees, 0 where
+ *                       a vector is zero (CellProfiler's arccos form is ill-conditioned at 0 and
+ *                       180 degrees and turns a rounding error above 1 into NaN)
+ * n = 1: every column is 0; n = 2: the Second columns and the angle are 0.  The closest columns
+ * do not depend on D and are repeated per scale, as CellProfiler does.  Integer arithmetic and
+ * integer LDS atomics only: two runs give the same bits.                                      */
+#define CPX_NB_NUMBER_OF_NEIGHBORS 0
+#define CPX_NB_PERCENT_TOUCHING 1
+#define CPX_NB_FIRST_CLOSEST_OBJECT_NUMBER 2
+#define CPX_NB_FIRST_CLOSEST_DISTANCE 3
+#define CPX_NB_SECOND_CLOSEST_OBJECT_NUMBER 4
+#define CPX_NB_SECOND_CLOSEST_DISTANCE 5
+#define CPX_NB_ANGLE_BETWEEN_NEIGHBORS 6
+#define CPX_N_NEIGHBORS 7
+#define CPX_NEIGHBORS_MAX_DISTANCE 32
+#define CPX_NEIGHBORS_MAX_SCALES 4
+/* the touch kernel's tile: core rows of a band and core columns of a segment (a window larger
+ * than that is walked tile by tile, each with a D halo: no object-size limit)                 */
+#define CPX_NEIGHBORS_BAND_ROWS 64
+#define CPX_NEIGHBORS_SEGMENT_COLS 64
+/* largest max_label: the neighbour-label bitmap (max_label + 1 bits) lives in LDS             */
+#define CPX_NEIGHBORS_MAX_LABEL 131071
+/* Columns of a neighbours row: CPX_N_NEIGHBORS * n_scales (0 for n_scales < 1).               */
+int cpx_n_neighbors(int n_scales);
+/* out_dev: float64 [B][max_label][CPX_N_NEIGHBORS * n_scales] (column CPX_N_NEIGHBORS * s + j);
+ * row k is the k-th object of the FOV's table (objects_dev / hdr_dev as cpx_objects wrote them
+ * for labels_dev; rows >= n_objects untouched).  distances: host array of n_scales integers,
+ * copied into the kernel arguments at enqueue (nothing reads host memory or allocates at launch,
+ * so the call can be captured into a graph).  A distance outside 1..CPX_NEIGHBORS_MAX_DISTANCE,
+ * n_scales outside 1..CPX_NEIGHBORS_MAX_SCALES or max_label > CPX_NEIGHBORS_MAX_LABEL is
+ * CPX_ERR_ARG without a launch.  A table row is trusted for its label, its centre and nothing
+ * that forms an address: bboxes and windows are cut to the plane.  Any object size; no
+ * workspace.  Runs on the context's current stream.                                           */
+int cpx_neighbors(cpx_ctx* ctx, const int32_t* labels_dev, int B, int H, int W, int max_label,
+                  const cpx_object* objects_dev, const cpx_fov_objects* hdr_dev, const int* distances,
+                  int n_scales, double* out_dev);
+
 /* ---- secondary objects for the Cells / Cytoplasm tables (Pycyto_pertime.py:46-49) -------- *
  * cells = skimage.segmentation.expand_labels(nuclei, distance) (0.18.3: nearest label pixel by
  * scipy's exact Euclidean feature transform, kept where the distance <= `distance`);
@@ -733,6 +795,11 @@ int cpx_fov_intensity_ext(cpx_ctx* ctx, const int32_t* labels_dev, int max_objec
  * objects and order as cpx_fov_features.                                                      */
 int cpx_fov_texture_haralick(cpx_ctx* ctx, const int32_t* labels_dev, int max_objects, double* host_out,
                              int* n_out);
+/* Neighbour rows (cpx_neighbors above) of every object of labels_dev at the submitted FOV's
+ * shape: host_out float64 [n][cpx_n_neighbors(n_scales)], the same objects and order as
+ * cpx_fov_features, the same bits as the batch entry.                                         */
+int cpx_fov_neighbors(cpx_ctx* ctx, const int32_t* labels_dev, int max_objects, const int* distances,
+                      int n_scales, double* host_out, int* n_out);
 int cpx_fov_wait(cpx_ctx* ctx);
 
 /* ---- profiling: device time of the k_tex_glcm launches (bench.py's GLCM LDS roofline) ----- *
